@@ -5,7 +5,7 @@ BASELINE.json metric: "images/sec (whole node) MNIST LeNet-5 at 1/2/4/8 MI355X"
 on synthetic 28x28x1 data with random-init weights; the per-GPU batch defaults
 to the BASELINE stress config (65536 / GPU, weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model lenet5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model lenet5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,6 +14,13 @@ normalise (K10), forward, softmax-CE, backward, RCCL all-reduce of the gradient
 buckets (N > 1), fused SGD + weight-EMA update, loss-EMA/step finalisation.
 K steps are bracketed by barrier + device synchronize on both sides; the
 reported time is the MAX over ranks; rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything
+measured or checked besides the headline figure (the eager twin of a hipGraph run,
+the per-phase breakdown, the replica check, the per-bucket all-reduce probe, the
+process-group report) runs after the timed steps only under --full.
+--dump-outputs DIR writes what the last timed step left (parameters, optimizer
+slots, step counter, loss statistics) as DIR/<name>.npy, before any --full extra.
 """
 from __future__ import annotations
 
@@ -34,6 +41,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: --eager_steps, "
+                         "--phases, --comm_probe, the replica check and the process-group report (off: those "
+                         "fields are null)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR",
+                    help="after the timed steps write the state the last timed step produced (params, mom, ema, "
+                         "step, stats, loss_ema) as DIR/<name>.npy (float32 / float64, rank 0; at most "
+                         "64 MB in all: a larger array is stored as a fixed seeded sample)")
     ap.add_argument("--prewarm_steps", type=int, default=200,
                     help="steady-state ramp before the W warmup steps: this many steps of the real step on the "
                          "real buffers, then the model, optimizer, loss and loader state is restored bitwise, so "
@@ -88,16 +103,16 @@ def parse():
                          "parameters per shard, ipc above); shm = CPU PS on pinned shared memory; ipc = xGMI peer "
                          "copies into a GPU PS; host = gloo, host-staged")
     ap.add_argument("--eager_steps", type=int, default=-1,
-                    help="N=1 with a hipGraph: also time this many EAGER steps after the timed region "
+                    help="--full, N=1 with a hipGraph: also time this many EAGER steps after the timed region "
                          "(ms_per_step_eager, comparable with N>1 runs); -1 = --steps")
     ap.add_argument("--comm_probe", type=int, default=1,
-                    help="N>1 (or --force_collectives 1): after the timed steps, time each gradient bucket's "
+                    help="--full, N>1 (or --force_collectives 1): after the timed steps, time each gradient bucket's "
                          "all-reduce alone (us, bus GB/s) and the exposed communication of an eager step")
     ap.add_argument("--lenet_bwd", default="fused", choices=["fused", "split"],
                     help="LeNet-5 conv-stack backward: fused = one kernel (lenet_bwd.hip); split = the three "
                          "per-layer convpool kernels (conv2 dgrad, conv2 / conv1 weight gradients)")
     ap.add_argument("--phases", type=int, default=3,
-                    help="extra eager steps AFTER the timed region, timed per phase with HIP events (0 = off)")
+                    help="--full: extra eager steps AFTER the timed region, timed per phase with HIP events (0 = off)")
     return ap.parse_args()
 
 
@@ -146,6 +161,38 @@ def prewarm_steps(net, loader, step, n: int) -> int:
     loader._ahead = None       # the next next() gathers its batch itself
     torch.cuda.synchronize()
     return n
+
+
+DUMP_CAP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path: str, tensors: dict) -> None:
+    """``tensors``: name -> tensor as the last timed step left it.  Written as float32 (float64
+    for float64 / integer tensors) ``path/<name>.npy``.  The byte budget is split evenly; an
+    array over its share is replaced by the elements at a fixed seeded index sample (sorted),
+    the same from run to run and from build to build."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(tensors))
+    for name, t in tensors.items():
+        t = t.detach().reshape(-1).cpu()
+        t = t.to(torch.float32 if t.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float64)
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            g = torch.Generator().manual_seed(0x5EED)
+            t = t[torch.randperm(t.numel(), generator=g)[:keep].sort().values]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+
+
+def step_outputs(net) -> dict:
+    """What a caller of the timed step receives: the updated flat parameters, the optimizer's
+    momentum and EMA slots, the global step, and the loss statistics / loss EMAs."""
+    import torch
+    fp = getattr(net, "fp", None)
+    out = {k: getattr(fp, k, None) for k in ("params", "mom", "ema", "step")}
+    out.update(stats=getattr(net, "stats", None), loss_ema=getattr(net, "loss_ema", None))
+    return {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
 
 
 def pg_block(dev, t_local: float):
@@ -257,6 +304,9 @@ def run_ps(args) -> int:
             "transport_used": ps.tx.name,
             "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"params": ps.fp.params, "mom": ps.fp.mom, "ema": ps.fp.ema,
+                                             "step": ps.fp.step})
         comms = [None] * world
         dist.gather_object(None, comms, dst=0)
         # per GRAD message, per worker: push (stage + copy + announce) host us and GB/s, the
@@ -412,11 +462,13 @@ def main() -> int:
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     el = float(elapsed.item())
-    # N > 1 (or the one-rank RCCL rehearsal): what the process group itself saw
-    pg = pg_block(dev, t1 - t0) if dist.is_initialized() else None
+    if args.dump_outputs and rank == 0:    # the last timed step's results, before any --full step
+        dump_outputs(args.dump_outputs, step_outputs(net))
+    # --full, N > 1 (or the one-rank RCCL rehearsal): what the process group itself saw
+    pg = pg_block(dev, t1 - t0) if args.full and dist.is_initialized() else None
     eager_ms = None
     n_eager = args.steps if args.eager_steps < 0 else args.eager_steps
-    if graph is not None and n_eager > 0:   # outside the timed region: the same step, eager
+    if args.full and graph is not None and n_eager > 0:   # outside the timed region: the same step, eager
         torch.cuda.synchronize()
         te = time.perf_counter()
         for _ in range(n_eager):
@@ -426,14 +478,14 @@ def main() -> int:
         eager_ms = (time.perf_counter() - te) / n_eager * 1e3
     stats = net.read_stats()
     in_sync = None
-    if world > 1:                           # outside the timed region: replicas must hold identical weights
+    if args.full and world > 1:             # outside the timed region: replicas must hold identical weights
         ck = net.fp.params.double().sum().reshape(1)
         lo, hi = ck.clone(), ck.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         in_sync = bool((hi - lo).abs().item() == 0.0)
     comm = None
-    if collectives and args.comm_probe:     # outside the timed region, after the replica check
+    if args.full and collectives and args.comm_probe:     # outside the timed region, after the replica check
         #  each bucket's all-reduce alone, then the exposed communication:
         # eager steps with the collectives on vs off (the off steps let replicas drift:
         # nothing after this reads the weights)
@@ -463,7 +515,7 @@ def main() -> int:
         comm.update({"eager_ms_comm_on": round(on, 4), "eager_ms_comm_off": round(off, 4),
                      "comm_exposed_ms": round(on - off, 4)})
     phases = None
-    if args.phases > 0:                     # outside the timed region: per-phase breakdown of an eager step
+    if args.full and args.phases > 0:       # outside the timed region: per-phase breakdown of an eager step
         from distributed_tensorflow_ibm_mnist_amd.runtime.timers import PhaseTimer
         timer = PhaseTimer(dev)
         for _ in range(args.phases):
@@ -485,6 +537,7 @@ def main() -> int:
             "warmup": args.warmup,
             "prewarm_ms": args.prewarm_ms,
             "prewarm_steps": n_pre,
+            "full": args.full,
             "ms_per_step": round(ms, 4),
             "higher_is_better": True,
             "scaling": "weak",

@@ -23,7 +23,7 @@ def test_bench_torchrun_two_ranks_one_gpu(model, batch):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", port,
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--model", model, "--batch", str(batch), "--dist_backend", "gloo", "--phases", "0"]
+           "--model", model, "--batch", str(batch), "--dist_backend", "gloo", "--phases", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT,
                        env={**os.environ, "OMP_NUM_THREADS": "2"})
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -56,7 +56,7 @@ def test_bench_one_rank_rccl_comm_probe():
     and the exposed-communication measurement run on a real RCCL process group."""
     port = str(29800 + (os.getpid() % 50))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--batch", "4096",
-           "--force_collectives", "1", "--phases", "0", "--graph", "0"]
+           "--force_collectives", "1", "--phases", "0", "--graph", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT,
                        env={**os.environ, "OMP_NUM_THREADS": "2", "MASTER_PORT": port})
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
