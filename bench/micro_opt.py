@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Time the fused optimizer launch alone, per update rule, on the reference CNN's parameters
+(3.46 M, with the bf16 / W^T copies the executor keeps): 200 launches between two device events
+after a warm-up, one settled run per rule, rules interleaved over a few rounds in one process.
+
+The launch is memory-bound.  Per element it reads params, grads, EMA and the rule's slots and
+writes params, EMA, the slots and (weights) a bf16 copy:
+
+    momentum          4 reads + 3 writes of 4 B + 2 B bf16 = 30 B
+    adam / rmsprop    5 reads + 4 writes of 4 B + 2 B bf16 = 38 B     (expected 38 / 30 = 1.27 x momentum)
+    adagrad           as momentum: one slot                = 30 B
+    sgd               3 reads + 2 writes of 4 B + 2 B bf16 = 22 B
+
+    python bench/micro_opt.py [--launches 200] [--rounds 5] [--model reference_cnn]
+prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BYTES = {"sgd": 22, "momentum": 30, "adam": 38, "rmsprop": 38, "adagrad": 30}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="reference_cnn")
+    ap.add_argument("--in_channels", type=int, default=3)
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--rules", default="momentum,adam,rmsprop,adagrad")
+    args = ap.parse_args()
+
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("micro_opt.py times a GPU launch: no HIP device")   # no CPU fall-back: it would say nothing
+    from distributed_tensorflow_ibm_mnist_amd.models import get_model
+    from distributed_tensorflow_ibm_mnist_amd.models.torch_ref import init_params
+    from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet
+    from distributed_tensorflow_ibm_mnist_amd.runtime.params import OptConfig
+
+    dev = torch.device("cuda", 0)
+    spec = get_model(args.model, args.in_channels)
+    init = init_params(spec, seed=0)
+    rules = [r for r in args.rules.split(",") if r]
+    nets = {}
+    for r in rules:
+        if r in ("adam", "rmsprop", "adagrad"):
+            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r)
+        else:
+            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, momentum=0.9 if r != "sgd" else 0.0, use_momentum=r != "sgd")
+        net = HipNet(spec, 16, dev, init, cfg)      # the executor's own FlatParams layout (pads, W^T copies)
+        net.fp.grads.copy_(torch.randn(net.fp.total, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+                           * 1e-2)
+        nets[r] = net
+    n = nets[rules[0]].fp.total
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = {r: [] for r in rules}
+    for rnd in range(args.rounds):
+        for r in rules:
+            fp, cfg = nets[r].fp, nets[r].opt
+            for _ in range(args.warmup):
+                fp.apply(cfg)
+            torch.cuda.synchronize()
+            ev0.record()
+            for _ in range(args.launches):
+                fp.apply(cfg)
+            ev1.record()
+            torch.cuda.synchronize()
+            times[r].append(ev0.elapsed_time(ev1) * 1e3 / args.launches)     # us per launch
+    for r in rules:
+        assert torch.isfinite(nets[r].fp.params).all(), r
+    out = {"metric": "fused optimizer launch, us (device events, back-to-back launches)", "model": args.model,
+           "parameters": n, "launches": args.launches, "rounds": args.rounds, "device": torch.cuda.get_device_name(0),
+           "rules": {}}
+    for r in rules:
+        med = statistics.median(times[r])
+        out["rules"][r] = {"us_median": round(med, 2), "us_min": round(min(times[r]), 2),
+                           "us_all": [round(t, 2) for t in times[r]], "bytes_per_element": BYTES[r],
+                           "GBps": round(n * BYTES[r] / med / 1e3, 1)}
+    if "momentum" in out["rules"]:
+        base = out["rules"]["momentum"]["us_median"]
+        for r in rules:
+            out["rules"][r]["ratio_to_momentum"] = round(out["rules"][r]["us_median"] / base, 3)
+            out["rules"][r]["expected_ratio"] = round(BYTES[r] / BYTES["momentum"], 3)
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -6,7 +6,7 @@ steps, measures top-1 accuracy on a fixed probe of ``--probe`` TRAINING images
 (forward only, same kernels).  Reports the first global step at which the probe
 accuracy reaches ``--target`` (default 0.99), plus wall time and images seen.
 
-    python bench/steps_to_acc.py [--batch 128] [--lr 0.01] [--optimizer momentum]
+    python bench/steps_to_acc.py [--batch 128] [--lr 0.01] [--optimizer momentum|adam|...]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         bench/steps_to_acc.py ...          (data parallel: global batch = N x batch)
     python bench/steps_to_acc.py --cpu --impl torch --model mlp     (CPU plumbing)
@@ -35,7 +35,8 @@ def parse(argv=None):
     ap.add_argument("--model", default="lenet5", choices=sorted(LABEL))
     ap.add_argument("--in_channels", type=int, default=1)
     ap.add_argument("--batch", type=int, default=128, help="per-rank batch")
-    ap.add_argument("--optimizer", default="momentum", choices=["sgd", "momentum", "nesterov"])
+    ap.add_argument("--optimizer", default="momentum", choices=["sgd", "momentum", "nesterov", "adam", "rmsprop", "adagrad"],
+                    help="adam / rmsprop / adagrad: TF1 defaults (pass a matching --lr, e.g. 0.001 for adam)")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
@@ -77,8 +78,11 @@ def run(args) -> dict:
         if world > 1:
             dist.init_process_group("nccl", device_id=dev)
     spec = get_model(args.model, args.in_channels)
-    opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, momentum=0.9 if args.optimizer != "sgd" else 0.0,
-                    nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999)
+    if args.optimizer in ("adam", "rmsprop", "adagrad"):
+        opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule=args.optimizer)
+    else:
+        opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, momentum=0.9 if args.optimizer != "sgd" else 0.0,
+                        nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999)
     init = init_params(spec, seed=args.seed)
     if args.impl == "hip":
         from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet

@@ -537,11 +537,30 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
                      double lr0, double decay_rate, int64_t decay_steps, double momentum, bool nesterov,
                      bool use_momentum, double grad_scale, double ema_max, optional<Tensor> l2,
                      optional<Tensor> guard, int64_t guard_want, optional<Tensor> guard_err, int64_t guard_id,
-                     optional<py::tuple> fin, optional<py::tuple> perm) {
+                     optional<py::tuple> fin, optional<py::tuple> perm, const std::string& rule,
+                     optional<Tensor> slot2, double beta1, double beta2, optional<double> epsilon,
+                     double rmsprop_decay) {
   const int64_t total = params.numel();
   check(params, at::kFloat, total, "params");
   check(grads, at::kFloat, total, "grads");
-  if (use_momentum) check(mom, at::kFloat, total, "mom");
+  // rule: the classic names leave the choice to use_momentum / nesterov, as before
+  int rule_id = mnistx::OPT_CLASSIC;
+  if (rule == "adam") rule_id = mnistx::OPT_ADAM;
+  else if (rule == "rmsprop") rule_id = mnistx::OPT_RMSPROP;
+  else if (rule == "adagrad") rule_id = mnistx::OPT_ADAGRAD;
+  else TORCH_CHECK(rule == "sgd" || rule == "momentum" || rule == "nesterov",
+                   "fused_optimizer: unknown rule '", rule, "' (sgd|momentum|nesterov|adam|rmsprop|adagrad)");
+  const bool adaptive = rule_id != mnistx::OPT_CLASSIC;
+  const bool two_slots = rule_id == mnistx::OPT_ADAM || rule_id == mnistx::OPT_RMSPROP;
+  if (use_momentum || adaptive) check(mom, at::kFloat, total, "mom");
+  if (two_slots) {
+    TORCH_CHECK(slot2.has_value() && slot2->defined(), "fused_optimizer: rule '", rule, "' needs slot2");
+    check(*slot2, at::kFloat, total, "slot2");
+    TORCH_CHECK(slot2->data_ptr() != mom.data_ptr(), "slot2 aliases mom");
+  }
+  if (rule_id == mnistx::OPT_ADAM)
+    TORCH_CHECK(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1, "adam: beta1, beta2 in [0, 1)");
+  if (rule_id == mnistx::OPT_RMSPROP) TORCH_CHECK(rmsprop_decay >= 0 && rmsprop_decay <= 1, "rmsprop: decay in [0, 1]");
   if (ema_max >= 0) check(ema, at::kFloat, total, "ema");
   check(step, at::kLong, 1, "step");
   TORCH_CHECK(!segs.is_cuda() && segs.scalar_type() == at::kLong && segs.dim() == 2 && segs.size(1) == 14,
@@ -597,6 +616,20 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
   op.use_momentum = use_momentum ? 1 : 0;
   op.grad_scale = (float)grad_scale;
   op.ema_max = (float)ema_max;
+  op.rule = rule_id;
+  if (rule_id == mnistx::OPT_ADAM) {
+    op.b1 = (float)beta1;
+    op.omb1 = (float)(1.0 - beta1);
+    op.b2 = (float)beta2;
+    op.omb2 = (float)(1.0 - beta2);
+    op.eps = (float)epsilon.value_or(1e-8);
+    op.log_b1 = beta1 > 0 ? std::log(beta1) : -1e300;   // beta = 0: b^t = 0, the correction is 1
+    op.log_b2 = beta2 > 0 ? std::log(beta2) : -1e300;
+  } else if (rule_id == mnistx::OPT_RMSPROP) {
+    op.b2 = (float)rmsprop_decay;
+    op.omb2 = (float)(1.0 - rmsprop_decay);
+    op.eps = (float)epsilon.value_or(1e-10);
+  }
   if (guard.has_value() && guard->defined()) {   // PS push guard: int64 stamp on the device
     check(*guard, at::kLong, 1, "guard");
     TORCH_CHECK(guard_err.has_value() && guard_err->defined(), "guard needs guard_err");
@@ -643,10 +676,11 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
     pj.h = (int)h;
     pj.n = (int)out.numel();
   }
-  hip_ok(mnistx::fused_optimizer(P<float>(params), P<const float>(grads), use_momentum ? P<float>(mom) : nullptr,
+  hip_ok(mnistx::fused_optimizer(P<float>(params), P<const float>(grads),
+                                 (use_momentum || adaptive) ? P<float>(mom) : nullptr,
                                  ema_max >= 0 ? P<float>(ema) : nullptr, BFm(bf), sv.data(), nseg, total,
                                  P<const int64_t>(step), op, l2p, l2n, cur_stream(), has_fin ? &fa : nullptr,
-                                 has_perm ? &pj : nullptr),
+                                 has_perm ? &pj : nullptr, two_slots ? P<float>(*slot2) : nullptr),
          "fused_optimizer");
 }
 
@@ -1359,7 +1393,9 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("decay_steps"), py::arg("momentum"), py::arg("nesterov"), py::arg("use_momentum"),
         py::arg("grad_scale"), py::arg("ema_max"), py::arg("l2") = py::none(), py::arg("guard") = py::none(),
         py::arg("guard_want") = 0, py::arg("guard_err") = py::none(), py::arg("guard_id") = 0,
-        py::arg("fin") = py::none(), py::arg("perm") = py::none());
+        py::arg("fin") = py::none(), py::arg("perm") = py::none(), py::kw_only(), py::arg("rule") = "sgd",
+        py::arg("slot2") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+        py::arg("epsilon") = py::none(), py::arg("rmsprop_decay") = 0.9);
   m.def("set_opt_fin_fused", [](int64_t on) { mnistx::set_opt_fin_fused((int)on); },
         "A/B switch of the optimizer launch running the step's finalize (MNISTX_OPT_FIN_FUSED)");
   m.def("opt_fin_fused_enabled", []() { return mnistx::opt_fin_fused_enabled() != 0; });

@@ -353,7 +353,18 @@ struct OptParams {
   int64_t guard_want;
   int* guard_err;
   int guard_id;
+  // update rule (OPT_*) and the adaptive rules' constants (TF1 semantics, t = step + 1):
+  //   Adam:    m = b1 m + omb1 g; v = b2 v + omb2 g^2;
+  //            p -= lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps)      slots: mom = m, slot2 = v
+  //   RMSProp: ms = b2 ms + omb2 g^2; mom = momentum mom + lr g / sqrt(ms + eps); p -= mom
+  //                                                                         slots: mom, slot2 = ms
+  //   Adagrad: acc += g^2; p -= lr g / sqrt(acc)                            slot: mom = acc
+  int rule;
+  float b1, omb1, b2, omb2;   // decay rates and their complements (rounded from double on the host)
+  float eps;
+  double log_b1, log_b2;      // Adam: log(beta), for the bias corrections -expm1(t log beta)
 };
+enum { OPT_CLASSIC = 0, OPT_ADAM = 1, OPT_RMSPROP = 2, OPT_ADAGRAD = 3 };   // OPT_CLASSIC: SGD / momentum / Nesterov
 
 // l2 (optional): [l2n per-tensor sums | fused_optimizer_blocks() per-block partials]
 int fused_optimizer_blocks(const OptSeg* segs, int nseg);
@@ -387,9 +398,10 @@ struct PermJob {
   int h, n, blk0;
 };
 // perm (optional): run that job in the same launch
+// slot2: the second slot buffer, needed by op.rule = OPT_ADAM / OPT_RMSPROP (which also need mom)
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
                            int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n, hipStream_t st,
-                           const FinArgs* fin = nullptr, const PermJob* perm = nullptr);
+                           const FinArgs* fin = nullptr, const PermJob* perm = nullptr, float* slot2 = nullptr);
 void set_opt_fin_fused(int on);
 int opt_fin_fused_enabled();
 // l2r (optional, device int32 [nw][3] = {weight index, first block, end block}): sum the

@@ -899,151 +899,20 @@ __global__ __launch_bounds__(TPB) void fused_opt_k(float* __restrict__ params, c
                                                    bf16_t* __restrict__ bf, SegTable tab,
                                                    const int64_t* __restrict__ step_p, OptParams op,
                                                    float* __restrict__ l2, FinArgs fin, PermJob pj) {
-  __shared__ float red[TPB / 64];
-  __shared__ float wsum[FIN_MAXW];
-  __shared__ int last;
-  const int nopt = pj.n > 0 ? pj.blk0 : (int)gridDim.x;   // optimizer blocks; the rest: the perm job
-  if ((int)blockIdx.x >= nopt) {
-    perm_one(((int)blockIdx.x - nopt) * TPB + threadIdx.x, pj.out, pj.start, pj.n, pj.N, pj.seed, pj.h, pj.lab_src,
-             pj.lab_out);
-    return;
-  }
-  if (op.guard && *op.guard != op.guard_want) {   // a stale / torn PS push: never applied
-    if (blockIdx.x == 0 && threadIdx.x == 0) *op.guard_err = op.guard_id;
-    return;
-  }
-  int si = 0;
-  while (si + 1 < tab.n && (int)blockIdx.x >= tab.blk0[si + 1]) ++si;
-  const OptSeg sg = tab.s[si];
-  const int64_t step = *step_p;
-  float lr = op.lr0;
-  if (op.decay_steps > 0) lr *= powf(op.decay_rate, (float)(step / op.decay_steps));  // staircase
-  float ema_d = 0.f;
-  if (op.ema_max >= 0.f) ema_d = fminf(op.ema_max, (1.f + (float)step) / (10.f + (float)step));
-  const int64_t lo = (int64_t)(blockIdx.x - tab.blk0[si]) * OPT_CHUNK;
-  const int64_t ij = (int64_t)sg.I * sg.J;
-  float sq = 0.f;
-  // each thread owns a PAIR of consecutive elements (8-byte loads / stores of params, grads,
-  // momentum and EMA; one 4-byte bf16 store when the pair stays in one row of the padded
-  // copy), all loads issued before any use; the pair falls back to two scalar accesses in a
-  // segment at an odd offset.  Out-of-range elements load element 0 and are never stored.
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  const int64_t li0 = lo + 2 * (int64_t)threadIdx.x;
-  const bool vec = (sg.off & 1) == 0 && li0 + 1 < sg.n;
-  float pv[OPT_EPT], gv[OPT_EPT], mv[OPT_EPT], ev[OPT_EPT];
-  if (vec) {
-    const int64_t e = sg.off + li0;
-    const f32x2_t p2 = *(const f32x2_t*)(params + e), g2 = *(const f32x2_t*)(grads + e);
-    const f32x2_t m2 = op.use_momentum ? *(const f32x2_t*)(mom + e) : f32x2_t{0.f, 0.f};
-    const f32x2_t e2 = op.ema_max >= 0.f ? *(const f32x2_t*)(ema + e) : f32x2_t{0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < OPT_EPT; ++u) {
-      pv[u] = p2[u];
-      gv[u] = g2[u];
-      mv[u] = m2[u];
-      ev[u] = e2[u];
-    }
-  } else {
-#pragma unroll
-    for (int u = 0; u < OPT_EPT; ++u) {
-      const int64_t li = li0 + u;
-      const int64_t e = sg.off + (li < sg.n ? li : 0);
-      pv[u] = params[e];
-      gv[u] = grads[e];
-      mv[u] = op.use_momentum ? mom[e] : 0.f;
-      ev[u] = op.ema_max >= 0.f ? ema[e] : 0.f;
-    }
-  }
-  float po[OPT_EPT], mo[OPT_EPT], eo[OPT_EPT];
-#pragma unroll
-  for (int u = 0; u < OPT_EPT; ++u) {
-    float p = pv[u];
-    if (li0 + u < sg.n) sq += p * p;
-    const float g = gv[u] * op.grad_scale + sg.wd * p;
-    float upd = g;
-    mo[u] = 0.f;
-    if (op.use_momentum) {
-      const float v = mv[u] * op.momentum + g;
-      mo[u] = v;
-      upd = op.nesterov ? g + op.momentum * v : v;
-    }
-    p -= lr * upd;
-    po[u] = p;
-    eo[u] = op.ema_max >= 0.f ? ev[u] - (1.f - ema_d) * (ev[u] - p) : 0.f;
-  }
-  if (vec) {
-    const int64_t e = sg.off + li0;
-    *(f32x2_t*)(params + e) = f32x2_t{po[0], po[1]};
-    if (op.use_momentum) *(f32x2_t*)(mom + e) = f32x2_t{mo[0], mo[1]};
-    if (op.ema_max >= 0.f) *(f32x2_t*)(ema + e) = f32x2_t{eo[0], eo[1]};
-  } else {
-#pragma unroll
-    for (int u = 0; u < OPT_EPT; ++u) {
-      if (li0 + u >= sg.n) continue;
-      const int64_t e = sg.off + li0 + u;
-      params[e] = po[u];
-      if (op.use_momentum) mom[e] = mo[u];
-      if (op.ema_max >= 0.f) ema[e] = eo[u];
-    }
-  }
-  if (sg.bf_off >= 0) {
-    // 32-bit magic-number divisions (segments < 2^31 elements): the 64-bit divides here
-    // were most of this kernel's time on the 3.2M-element local3 weights
-    int64_t bi[OPT_EPT];
-    int jj0 = 0, ii0 = 0;
-#pragma unroll
-    for (int u = 0; u < OPT_EPT; ++u) {
-      const int l32 = (int)(li0 + u);
-      const int gg = tab.fij[si].div(l32);
-      const int rem = l32 - gg * (int)ij;
-      const int ii = tab.fj[si].div(rem), jj = rem - ii * sg.J;
-      bi[u] = sg.bf_off + ((int64_t)gg * sg.Ip + ii) * sg.Jp + jj;
-      if (u == 0) {
-        jj0 = jj;
-        ii0 = ii;
-      }
-    }
-    const bf16_t b0 = f2bf(po[0]), b1 = f2bf(po[1]);
-    if (vec && bi[1] == bi[0] + 1 && (bi[0] & 1) == 0) {
-      *(uint32_t*)(bf + bi[0]) = (uint32_t)b0 | ((uint32_t)b1 << 16);
-    } else {
-      if (li0 < sg.n) bf[bi[0]] = b0;
-      if (li0 + 1 < sg.n) bf[bi[1]] = b1;
-    }
-    if (sg.bft_off >= 0) {   // W^T copy (fused dense head): scattered 2-byte stores
-      if (li0 < sg.n) bf[sg.bft_off + (int64_t)jj0 * sg.It + ii0] = b0;
-      if (li0 + 1 < sg.n) {
-        const int l32 = (int)(li0 + 1);
-        const int gg = tab.fij[si].div(l32);
-        const int rem = l32 - gg * (int)ij;
-        const int ii = tab.fj[si].div(rem), jj = rem - ii * sg.J;
-        bf[sg.bft_off + (int64_t)jj * sg.It + ii] = b1;
-      }
-    }
-  }
-  if (l2 && sg.track_l2) {
-    // per-block partial, summed in block order by finalize_k: one float atomic per
-    // block on ONE address serialised ~6.8K blocks (96 us of the reference CNN's
-    // update) and made the weight-decay loss order-dependent
-    sq = warp_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int w = 0; w < TPB / 64; ++w) t += red[w];
-      if (fin.ticket) st_coh(l2 + tab.l2n + blockIdx.x, t);
-      else l2[tab.l2n + blockIdx.x] = t;
-    }
-  }
-  if (!fin.ticket) return;
-  // the step's finalize in this launch: the last block to take a ticket (thread 0, after its
-  // coherent partial store) runs it, reading the partials coherently; every block has read
-  // *step_p by now
-  if (threadIdx.x == 0) last = take_ticket(fin.ticket) == nopt - 1;
-  __syncthreads();
-  if (!last) return;
-  if (threadIdx.x == 0) *fin.ticket = 0;
-  finalize_body<true>(fin, wsum);
+  constexpr int RULE = OPT_CLASSIC;   // SGD / momentum / Nesterov, chosen at run time by OptParams
+  float* const slot2 = nullptr;
+#include "fused_opt_body.h"
+}
+
+// Adam / RMSProp / Adagrad (OptParams): the same body with the rule fixed at compile time and a
+// second slot pointer
+template <int RULE>
+__global__ __launch_bounds__(TPB) void adaptive_opt_k(float* __restrict__ params, const float* __restrict__ grads,
+                                                      float* __restrict__ mom, float* __restrict__ slot2,
+                                                      float* __restrict__ ema, bf16_t* __restrict__ bf, SegTable tab,
+                                                      const int64_t* __restrict__ step_p, OptParams op,
+                                                      float* __restrict__ l2, FinArgs fin, PermJob pj) {
+#include "fused_opt_body.h"
 }
 
 // stats: [0] ce_sum acc [1] correct acc [2] nan flag [3] -
@@ -1476,8 +1345,10 @@ hipError_t finalize_step(const FinArgs& f, hipStream_t st) {
 
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
                            int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n,
-                           hipStream_t st, const FinArgs* fin, const PermJob* perm) {
+                           hipStream_t st, const FinArgs* fin, const PermJob* perm, float* slot2) {
   if (nseg > MAXSEG || nseg < 1) return hipErrorInvalidValue;
+  if (op.rule < OPT_CLASSIC || op.rule > OPT_ADAGRAD) return hipErrorInvalidValue;
+  if (op.rule != OPT_CLASSIC && (!mom || (op.rule != OPT_ADAGRAD && !slot2))) return hipErrorInvalidValue;
   if (fin && fin->nw > FIN_MAXW) return hipErrorInvalidValue;
   SegTable tab;
   int nb = 0;
@@ -1507,8 +1378,17 @@ hipError_t fused_optimizer(float* params, const float* grads, float* mom, float*
     pj.blk0 = nb;
     npb = (pj.n + TPB - 1) / TPB;
   }
-  hipLaunchKernelGGL(fused_opt_k, dim3(nb + npb), dim3(TPB), 0, st, params, grads, mom, ema, bf, tab, step, op, l2, fa,
-                     pj);
+  const dim3 grid(nb + npb);
+  auto adaptive = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj);
+  };
+  switch (op.rule) {
+    case OPT_ADAM: adaptive(adaptive_opt_k<OPT_ADAM>); break;
+    case OPT_RMSPROP: adaptive(adaptive_opt_k<OPT_RMSPROP>); break;
+    case OPT_ADAGRAD: adaptive(adaptive_opt_k<OPT_ADAGRAD>); break;
+    default:
+      hipLaunchKernelGGL(fused_opt_k, grid, dim3(TPB), 0, st, params, grads, mom, ema, bf, tab, step, op, l2, fa, pj);
+  }
   if (fin && !tickets) return finalize_step(*fin, st);
   return hipGetLastError();
 }

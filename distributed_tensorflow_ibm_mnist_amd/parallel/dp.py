@@ -225,8 +225,9 @@ class DataParallel:
         if self.world == 1:
             return
         fp = self.net.fp
-        for t in (fp.params, fp.ema, fp.mom, fp.step):
-            dist.broadcast(t, src, group=self.group)
+        for t in (fp.params, fp.ema, fp.mom, fp.slot2, fp.step):
+            if t is not None:   # slot2: only the rules with a second slot have one
+                dist.broadcast(t, src, group=self.group)
         fp.refresh_bf16()
 
     def global_stats(self) -> Dict[str, float]:

@@ -291,6 +291,7 @@ class HipNetF32:
             specs.append((f"{L.name}/weights", shp, L.wd))
             specs.append((f"{L.name}/biases", (L.cout if isinstance(L, Conv) else L.dout,), None))
         self.fp = FlatParams.build(specs, init, dev, bf16_copies=False)   # kernels read the fp32 masters
+        self.fp.init_slots(self.opt)
         H, W = spec.input_hw
         self.x0 = _f32(batch, H, W, spec.in_channels, device=dev)
         self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)

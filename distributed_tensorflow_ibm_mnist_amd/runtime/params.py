@@ -5,7 +5,8 @@ gradients, momentum slots and EMA shadows), laid out in the reference's
 creation order (``mnist_input.py:137-205``).  This gives:
 
 * one fused optimizer launch for every tensor (K9, ``csrc/kernels/misc.hip``):
-  L2 weight decay, SGD / momentum / Nesterov, the staircase LR schedule
+  L2 weight decay, SGD / momentum / Nesterov or Adam / RMSProp / Adagrad (TF1
+  semantics; a second slot buffer where the rule has one), the staircase LR schedule
   (``mnist_input.py:252-256``, read from the device-side global step — no host
   sync, hipGraph capturable), the weight EMA with TF's
   ``min(decay, (1+t)/(10+t))`` (``mnist_input.py:265-267``), and the refresh of
@@ -23,6 +24,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 
+ADAPTIVE_RULES = ("adam", "rmsprop", "adagrad")
+
+
 @dataclasses.dataclass
 class OptConfig:
     lr0: float = 0.1
@@ -32,19 +36,64 @@ class OptConfig:
     nesterov: bool = False
     use_momentum: bool = False
     ema_max: float = 0.9999       # MOVING_AVERAGE_DECAY (mnist_input.py:20); < 0 disables
+    # update rule: "sgd" (SGD / momentum / Nesterov as use_momentum and nesterov say) or one of
+    # the adaptive rules "adam" | "rmsprop" | "adagrad" (TF1 semantics and defaults).  With
+    # "rmsprop", ``momentum`` is RMSProp's own momentum (TF1 default 0.0).
+    rule: str = "sgd"
+    beta1: float = 0.9            # adam
+    beta2: float = 0.999          # adam
+    epsilon: Optional[float] = None   # None: the rule's TF1 default (adam 1e-8, rmsprop 1e-10)
+    rmsprop_decay: float = 0.9
+    adagrad_initial_accumulator: float = 0.1
+
+    def __post_init__(self):
+        if self.rule in ("momentum", "nesterov"):
+            self.rule = "sgd"
+        if self.rule not in ("sgd",) + ADAPTIVE_RULES:
+            raise ValueError(f"unknown update rule {self.rule!r} (sgd|{'|'.join(ADAPTIVE_RULES)})")
+        if self.rule == "adagrad" and not self.adagrad_initial_accumulator > 0:
+            raise ValueError("adagrad_initial_accumulator must be > 0")   # as TF1 requires
 
     @staticmethod
     def from_spec(spec, decay_steps: int, decay_rate: float, ema: float = 0.9999) -> "OptConfig":
         """From a parameter-manager ``OptimizerSpec``."""
         lr = spec.learning_rate
+        adaptive = spec.name in ADAPTIVE_RULES
         return OptConfig(lr0=float(lr), decay_rate=float(decay_rate), decay_steps=int(decay_steps),
                          momentum=float(spec.momentum), nesterov=bool(spec.nesterov),
-                         use_momentum=spec.name == "momentum", ema_max=ema)
+                         use_momentum=spec.name == "momentum", ema_max=ema,
+                         rule=spec.name if adaptive else "sgd", beta1=float(spec.beta1), beta2=float(spec.beta2),
+                         epsilon=None if spec.epsilon is None else float(spec.epsilon),
+                         rmsprop_decay=float(spec.rmsprop_decay),
+                         adagrad_initial_accumulator=float(spec.adagrad_initial_accumulator))
 
     def lr_at(self, step: int) -> float:
         if self.decay_steps <= 0:
             return self.lr0
         return self.lr0 * self.decay_rate ** (step // self.decay_steps)
+
+    @property
+    def adaptive(self) -> bool:
+        return self.rule in ADAPTIVE_RULES
+
+    @property
+    def eps(self) -> float:
+        return self.epsilon if self.epsilon is not None else {"adam": 1e-8, "rmsprop": 1e-10}.get(self.rule, 0.0)
+
+    def slot_names(self) -> Tuple[Optional[str], Optional[str]]:
+        """TF1's slot-variable suffixes of (``FlatParams.mom``, ``FlatParams.slot2``); None: unused."""
+        if self.rule == "adam":
+            return "Adam", "Adam_1"            # m, v
+        if self.rule == "rmsprop":
+            return "RMSProp_1", "RMSProp"      # mom, ms (TF1 creates the "rms" slot first)
+        if self.rule == "adagrad":
+            return "Adagrad", None             # accumulator
+        return ("Momentum" if self.use_momentum else None), None
+
+    def slot_init(self) -> Tuple[float, float]:
+        """Initial values of the two slots, as TF1 creates them."""
+        return (self.adagrad_initial_accumulator if self.rule == "adagrad" else 0.0,
+                1.0 if self.rule == "rmsprop" else 0.0)
 
 
 @dataclasses.dataclass
@@ -75,7 +124,10 @@ class FlatParams:
         self.device = device
         self.params = torch.zeros(total, dtype=torch.float32, device=device)
         self.grads = torch.zeros(total, dtype=torch.float32, device=device)
+        # slot buffers: mom = Momentum, Adam m, RMSProp mom or the Adagrad accumulator;
+        # slot2 = Adam v or RMSProp ms, allocated by init_slots() for those rules only
         self.mom = torch.zeros(total, dtype=torch.float32, device=device)
+        self.slot2: Optional[torch.Tensor] = None
         self.ema = torch.zeros(total, dtype=torch.float32, device=device)
         self.bf16 = torch.zeros(max(bf_total, 1), dtype=torch.bfloat16, device=device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
@@ -177,6 +229,22 @@ class FlatParams:
     def mom_view(self, name: str) -> torch.Tensor:
         return self._view(self.mom, name)
 
+    def slot_views(self, name: str) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(first slot, second slot or None) of one variable; which quantity each holds
+        depends on the rule (``OptConfig.slot_names``)."""
+        return self._view(self.mom, name), (None if self.slot2 is None else self._view(self.slot2, name))
+
+    def init_slots(self, cfg: OptConfig) -> None:
+        """Give the slots the rule's initial values, allocating the second slot buffer if the
+        rule has one.  The executors call this once at construction (before any graph
+        capture: the captured launch holds the buffer's address)."""
+        s1, s2 = cfg.slot_init()
+        self.mom.fill_(s1)
+        if cfg.rule in ("adam", "rmsprop"):
+            if self.slot2 is None:
+                self.slot2 = torch.empty(self.total, dtype=torch.float32, device=self.device)
+            self.slot2.fill_(s2)
+
     def ema_view(self, name: str) -> torch.Tensor:
         return self._view(self.ema, name)
 
@@ -195,7 +263,8 @@ class FlatParams:
     # -- state --------------------------------------------------------------
     def load_state(self, values: Dict[str, torch.Tensor], ema_too: bool = False,
                    ema_values: Optional[Dict[str, torch.Tensor]] = None,
-                   mom_values: Optional[Dict[str, torch.Tensor]] = None) -> None:
+                   mom_values: Optional[Dict[str, torch.Tensor]] = None,
+                   slot2_values: Optional[Dict[str, torch.Tensor]] = None) -> None:
         with torch.no_grad():
             for name, v in values.items():
                 self.param_view(name).copy_(v.reshape(self.by_name[name].shape))
@@ -205,6 +274,10 @@ class FlatParams:
                 self.ema_view(name).copy_(v.reshape(self.by_name[name].shape))
             for name, v in (mom_values or {}).items():
                 self.mom_view(name).copy_(v.reshape(self.by_name[name].shape))
+            if slot2_values:
+                assert self.slot2 is not None, "second-slot values for a rule without a second slot"
+                for name, v in slot2_values.items():
+                    self._view(self.slot2, name).copy_(v.reshape(self.by_name[name].shape))
         self.refresh_bf16()
 
     def refresh_bf16(self) -> None:
@@ -232,7 +305,16 @@ class FlatParams:
         in the same launch (HipNet.update); ``perm``: the next batch's perm_positions job
         (DeviceLoader.lookahead_job), run by extra blocks of the launch."""
         from ..ops._ext import kernels
+        l2 = self.l2 if (track_l2 and self.wd_entries) else None
+        if not cfg.adaptive:
+            kernels().fused_optimizer(self.params, self.grads, self.mom, self.ema, self.bf16, self.segs, self.step,
+                                      cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, cfg.nesterov,
+                                      cfg.use_momentum, grad_scale, cfg.ema_max, l2, fin=fin, perm=perm)
+            return
+        if cfg.rule != "adagrad" and self.slot2 is None:
+            raise RuntimeError(f"optimizer rule {cfg.rule!r} needs FlatParams.init_slots(cfg) before the first step")
         kernels().fused_optimizer(self.params, self.grads, self.mom, self.ema, self.bf16, self.segs, self.step,
-                                  cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, cfg.nesterov,
-                                  cfg.use_momentum, grad_scale, cfg.ema_max,
-                                  self.l2 if (track_l2 and self.wd_entries) else None, fin=fin, perm=perm)
+                                  cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, False, False,
+                                  grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, rule=cfg.rule, slot2=self.slot2,
+                                  beta1=cfg.beta1, beta2=cfg.beta2, epsilon=cfg.epsilon,
+                                  rmsprop_decay=cfg.rmsprop_decay)

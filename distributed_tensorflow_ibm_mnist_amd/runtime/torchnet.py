@@ -9,6 +9,7 @@ buckets and PS transfers are identical between the two implementations.
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -17,6 +18,29 @@ import torch.nn.functional as F
 from ..models import torch_ref
 from ..models.spec import Conv, Dense, ModelSpec
 from .params import FlatParams, OptConfig
+
+
+def _adaptive_update(fp: FlatParams, cfg: OptConfig, g: torch.Tensor, lr: float, t: int) -> None:
+    """Adam / RMSProp / Adagrad with TF1 semantics (the fused kernel's adaptive rules); the
+    slots are ``fp.mom`` and ``fp.slot2`` as ``OptConfig.slot_names`` lays them out."""
+    if cfg.rule == "adam":
+        m, v = fp.mom, fp.slot2
+        m.mul_(cfg.beta1).add_(g, alpha=1.0 - cfg.beta1)
+        v.mul_(cfg.beta2).add_(g * g, alpha=1.0 - cfg.beta2)
+        # bias corrections in double: fp32 1 - 0.999**t is off by 6e-5 at t = 1
+        c1 = -math.expm1(t * math.log(cfg.beta1)) if cfg.beta1 > 0 else 1.0
+        c2 = -math.expm1(t * math.log(cfg.beta2)) if cfg.beta2 > 0 else 1.0
+        # epsilon outside the root: m = v = 0 gives a zero update, never 0 * inf
+        fp.params.sub_(m / (v.sqrt() + cfg.eps), alpha=lr * math.sqrt(c2) / c1)
+    elif cfg.rule == "rmsprop":
+        mom, ms = fp.mom, fp.slot2
+        ms.mul_(cfg.rmsprop_decay).add_(g * g, alpha=1.0 - cfg.rmsprop_decay)
+        mom.mul_(cfg.momentum).add_(g / (ms + cfg.eps).sqrt(), alpha=lr)
+        fp.params.sub_(mom)
+    else:
+        acc = fp.mom
+        acc.add_(g * g)
+        fp.params.sub_(g / acc.sqrt(), alpha=lr)
 
 
 def torch_update(fp: FlatParams, cfg: OptConfig, grad_scale: float = 1.0) -> None:
@@ -32,12 +56,15 @@ def torch_update(fp: FlatParams, cfg: OptConfig, grad_scale: float = 1.0) -> Non
                 v = fp.params[e.off:e.off + e.n]
                 fp.l2[e.l2_index] += (v * v).sum()
         g = fp.grads * grad_scale + wd * fp.params
-        if cfg.use_momentum:
-            fp.mom.mul_(cfg.momentum).add_(g)
-            upd = g + cfg.momentum * fp.mom if cfg.nesterov else fp.mom
+        if cfg.adaptive:
+            _adaptive_update(fp, cfg, g, lr, step + 1)
         else:
-            upd = g
-        fp.params.sub_(lr * upd)
+            if cfg.use_momentum:
+                fp.mom.mul_(cfg.momentum).add_(g)
+                upd = g + cfg.momentum * fp.mom if cfg.nesterov else fp.mom
+            else:
+                upd = g
+            fp.params.sub_(lr * upd)
         if cfg.ema_max >= 0:
             d = min(cfg.ema_max, (1.0 + step) / (10.0 + step))
             fp.ema.sub_((1.0 - d) * (fp.ema - fp.params))
@@ -55,6 +82,7 @@ class TorchNet:
             specs.append((f"{L.name}/weights", shp, L.wd))
             specs.append((f"{L.name}/biases", (L.cout if isinstance(L, Conv) else L.dout,), None))
         self.fp = FlatParams.build(specs, init, dev)
+        self.fp.init_slots(self.opt)
         H, W = spec.input_hw
         self.autocast = (dev.type == "cuda") if autocast is None else autocast
         xdt = torch.bfloat16 if dev.type == "cuda" else torch.float32

@@ -40,15 +40,27 @@ def state_tensors(net, include_momentum: bool = True) -> Dict[str, np.ndarray]:
     out: Dict[str, np.ndarray] = {}
     params = fp.params.detach().cpu().numpy()
     ema = fp.ema.detach().cpu().numpy()
-    mom = fp.mom.detach().cpu().numpy()
+    # slot variables under TF1's names: <var>/Momentum; <var>/Adam (m), <var>/Adam_1 (v);
+    # <var>/RMSProp (ms), <var>/RMSProp_1 (mom); <var>/Adagrad
+    n1, n2 = net.opt.slot_names() if include_momentum else (None, None)
+    mom = fp.mom.detach().cpu().numpy() if n1 else None
+    slot2 = fp.slot2.detach().cpu().numpy() if n2 else None
     for e in fp.entries:
         sl = slice(e.off, e.off + e.n)
         out[e.name] = params[sl].reshape(e.shape).copy()
         if net.opt.ema_max >= 0:
             out[f"{e.name}/ExponentialMovingAverage"] = ema[sl].reshape(e.shape).copy()
-        if include_momentum and net.opt.use_momentum:
-            out[f"{e.name}/Momentum"] = mom[sl].reshape(e.shape).copy()
-    out["global_step"] = np.asarray(int(fp.step.item()), dtype=np.int64)
+        if n1:
+            out[f"{e.name}/{n1}"] = mom[sl].reshape(e.shape).copy()
+        if n2:
+            out[f"{e.name}/{n2}"] = slot2[sl].reshape(e.shape).copy()
+    step = int(fp.step.item())
+    if include_momentum and net.opt.rule == "adam":
+        # TF1's Adam keeps beta^t as variables; written as beta^(global_step + 1), ignored on
+        # restore (the update derives them from the step)
+        out["beta1_power"] = np.asarray(net.opt.beta1 ** (step + 1), dtype=np.float32)
+        out["beta2_power"] = np.asarray(net.opt.beta2 ** (step + 1), dtype=np.float32)
+    out["global_step"] = np.asarray(step, dtype=np.int64)
     le = net.loss_ema.detach().cpu().numpy().reshape(-1, 3)
     for i, name in enumerate(net.loss_names):
         out[f"{name}/avg"] = np.asarray(le[i, 2], dtype=np.float32)
@@ -65,9 +77,13 @@ def load_state(net, tensors: Dict[str, np.ndarray], strict: bool = True) -> int:
     vals = {n: torch.from_numpy(np.asarray(tensors[n])) for n in fp.names() if n in tensors}
     emas = {n: torch.from_numpy(np.asarray(tensors[f"{n}/ExponentialMovingAverage"])) for n in fp.names()
             if f"{n}/ExponentialMovingAverage" in tensors}
-    moms = {n: torch.from_numpy(np.asarray(tensors[f"{n}/Momentum"])) for n in fp.names()
-            if f"{n}/Momentum" in tensors}
-    fp.load_state(vals, ema_too=not emas, ema_values=emas, mom_values=moms)
+    # slots the checkpoint lacks keep their initial values, as TF would create them
+    n1, n2 = net.opt.slot_names()
+    n1 = n1 or "Momentum"
+    moms = {n: torch.from_numpy(np.asarray(tensors[f"{n}/{n1}"])) for n in fp.names() if f"{n}/{n1}" in tensors}
+    slot2 = {n: torch.from_numpy(np.asarray(tensors[f"{n}/{n2}"])) for n in fp.names()
+             if n2 and f"{n}/{n2}" in tensors}
+    fp.load_state(vals, ema_too=not emas, ema_values=emas, mom_values=moms, slot2_values=slot2)
     step = int(np.asarray(tensors.get("global_step", 0)))
     fp.step.fill_(step)
     le = net.loss_ema.view(-1, 3)

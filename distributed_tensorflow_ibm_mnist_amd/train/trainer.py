@@ -62,8 +62,9 @@ def placement_table(replica, cl: Cluster) -> str:
     dev = str(replica.device)
     lines = [f"device placement (rank {cl.rank}/{cl.world}, mode {cl.mode}, backend {cl.backend or 'none'}"
              + (f", PS data plane {cl.transport}" if cl.mode == "ps" else "") + "):"]
+    slots = "".join(f" + {s}" for s in net.opt.slot_names() if s)
     for e in net.fp.entries:
-        lines.append(f"  {e.name:34s} {str(e.shape):22s} fp32 master + EMA{' + Momentum' if net.opt.use_momentum else ''}"
+        lines.append(f"  {e.name:34s} {str(e.shape):22s} fp32 master + EMA{slots}"
                      f" -> {dev if cl.mode != 'ps' else 'ps shard'}")
     for lay in getattr(net, "layers", []):
         lines.append(f"  kernel {lay.name:18s} {type(lay).__name__:14s} -> {dev}")
@@ -73,11 +74,8 @@ def placement_table(replica, cl: Cluster) -> str:
 
 
 def train(FLAGS, log=print) -> Dict[str, float]:
-    pm.configure(FLAGS.config or None, **{k: v for k, v in {
-        "max_steps": FLAGS.max_steps, "test_interval": FLAGS.test_interval, "batch_size": FLAGS.batch_size,
-        "base_lr": FLAGS.base_lr, "lr_decay": FLAGS.lr_decay, "optimizer": FLAGS.optimizer,
-        "momentum": FLAGS.momentum, "train_data": FLAGS.train_data, "test_data": FLAGS.test_data,
-        "val_data": FLAGS.val_data}.items() if v not in (None, "", -1)})
+    pm.configure_from_flags(FLAGS)
+    pm.check_ps_optimizer(FLAGS.job_name, log)    # before setup_distribute opens any socket
     max_steps = pm.getMaxSteps()                  # main.py:38-40
     test_interval = pm.getTestInterval()
     batch_size = pm.getTrainBatchSize()

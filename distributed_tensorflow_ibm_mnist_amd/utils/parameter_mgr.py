@@ -39,8 +39,13 @@ DEFAULTS: Dict[str, Any] = {
     "batch_size": 128,
     "base_lr": 0.1,
     "lr_decay": 0.1,
-    "optimizer": "sgd",          # sgd | momentum | nesterov
-    "momentum": 0.9,
+    "optimizer": "sgd",          # sgd | momentum | nesterov | adam | rmsprop | adagrad
+    "momentum": 0.9,             # momentum | nesterov (rmsprop: 0.0 unless the config sets it)
+    "beta1": 0.9,                # adam (TF1 defaults)
+    "beta2": 0.999,
+    "epsilon": None,             # adam 1e-8, rmsprop 1e-10
+    "rmsprop_decay": 0.9,
+    "adagrad_initial_accumulator": 0.1,
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -52,10 +57,15 @@ ENV_VAR = "MNISTX_PARAMS"
 @dataclasses.dataclass(frozen=True)
 class OptimizerSpec:
     """What ``getOptimizer(lr)`` returns: enough to build the fused K9 update."""
-    name: str            # "sgd" | "momentum"
+    name: str            # "sgd" | "momentum" | "adam" | "rmsprop" | "adagrad"
     learning_rate: Any   # float, or a callable/step-schedule
     momentum: float = 0.0
     nesterov: bool = False
+    beta1: float = 0.9
+    beta2: float = 0.999
+    epsilon: Optional[float] = None   # None: the rule's TF1 default
+    rmsprop_decay: float = 0.9
+    adagrad_initial_accumulator: float = 0.1
 
 
 _config: Dict[str, Any] = {}
@@ -107,6 +117,28 @@ def configure(source: Union[None, str, Dict[str, Any]] = None, **overrides: Any)
     if unknown:
         raise ValueError(f"unknown parameter(s) in config: {sorted(unknown)}")
     _config = cfg
+
+
+FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", "optimizer", "momentum",
+             "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
+             "adagrad_initial_accumulator")
+ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
+
+
+def configure_from_flags(FLAGS) -> None:
+    """``--config`` (or ``MNISTX_PARAMS``) plus the override flags that are set ('' and -1: unset)."""
+    configure(getattr(FLAGS, "config", "") or None,
+              **{k: v for k, v in ((k, getattr(FLAGS, k, None)) for k in FLAG_KEYS) if v not in (None, "", -1)})
+
+
+def check_ps_optimizer(job_name: str, log=print) -> None:
+    """Parameter-server mode moves exactly one slot buffer between workers and servers, so the
+    adaptive rules are not available there: a PS or worker task exits at start-up."""
+    name = str(get("optimizer")).lower()
+    if job_name in ("ps", "worker") and name in ADAPTIVE_OPTIMIZERS:
+        log(f"optimizer {name!r} is not supported in parameter-server mode (--job_name={job_name}): use "
+            f"sgd|momentum|nesterov there; {'|'.join(ADAPTIVE_OPTIMIZERS)} run single-process and data-parallel")
+        raise SystemExit(2)
 
 
 def set_param(key: str, value: Any) -> None:
@@ -170,7 +202,21 @@ def getOptimizer(lr: Any) -> OptimizerSpec:
         return OptimizerSpec("momentum", lr, mom, False)
     if name == "nesterov":
         return OptimizerSpec("momentum", lr, mom, True)
-    raise ValueError(f"unsupported optimizer {name!r} (sgd|momentum|nesterov)")
+    eps = get("epsilon")
+    eps = None if eps is None else float(eps)
+    if name == "adam":
+        return OptimizerSpec("adam", lr, beta1=float(get("beta1")), beta2=float(get("beta2")), epsilon=eps)
+    if name == "rmsprop":
+        # TF1's RMSProp momentum defaults to 0.0: only a momentum the config itself sets applies,
+        # never the manager's general default
+        return OptimizerSpec("rmsprop", lr, momentum=float(_config["momentum"]) if "momentum" in _config else 0.0,
+                             epsilon=eps, rmsprop_decay=float(get("rmsprop_decay")))
+    if name == "adagrad":
+        acc0 = float(get("adagrad_initial_accumulator"))
+        if not acc0 > 0:
+            raise ValueError(f"adagrad_initial_accumulator must be > 0, got {acc0}")
+        return OptimizerSpec("adagrad", lr, adagrad_initial_accumulator=acc0)
+    raise ValueError(f"unsupported optimizer {name!r} (sgd|momentum|nesterov|adam|rmsprop|adagrad)")
 
 
 configure()

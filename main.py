@@ -38,8 +38,14 @@ flags.DEFINE_integer("test_interval", -1, "override getTestInterval()")
 flags.DEFINE_integer("batch_size", -1, "override getTrainBatchSize() (per replica)")
 flags.DEFINE_float("base_lr", -1, "override getBaseLearningRate()")
 flags.DEFINE_float("lr_decay", -1, "override getLearningRateDecay()")
-flags.DEFINE_string("optimizer", "", "override getOptimizer(): sgd | momentum | nesterov")
-flags.DEFINE_float("momentum", -1, "momentum for --optimizer=momentum|nesterov")
+flags.DEFINE_string("optimizer", "", "override getOptimizer(): sgd | momentum | nesterov | adam | rmsprop | adagrad "
+                    "(the adaptive three: TF1 semantics and defaults; not in parameter-server mode)")
+flags.DEFINE_float("momentum", -1, "momentum for --optimizer=momentum|nesterov; with rmsprop, its momentum (default 0)")
+flags.DEFINE_float("beta1", -1, "adam: override beta1 (0.9)")
+flags.DEFINE_float("beta2", -1, "adam: override beta2 (0.999)")
+flags.DEFINE_float("epsilon", -1, "adam / rmsprop: override epsilon (1e-8 / 1e-10)")
+flags.DEFINE_float("rmsprop_decay", -1, "rmsprop: override the decay of the mean square (0.9)")
+flags.DEFINE_float("adagrad_initial_accumulator", -1, "adagrad: override the accumulator's initial value (0.1)")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
@@ -82,6 +88,10 @@ flags.DEFINE_float("collective_timeout", 600.0, "process-group timeout (s): a hu
 
 
 def main(argv=None):
+    # a PS / worker task with an adaptive optimizer stops here, before torch is even imported
+    from distributed_tensorflow_ibm_mnist_amd.utils import parameter_mgr
+    parameter_mgr.configure_from_flags(FLAGS)
+    parameter_mgr.check_ps_optimizer(FLAGS.job_name)
     if FLAGS.ps_hosts and FLAGS.job_name in ("ps", "worker") and "GPU_MAX_HW_QUEUES" not in os.environ:
         # PS mode only (data-parallel workers keep HIP's default queues, so the RCCL stream
         # does not share a queue with compute): PS tasks are often co-located on one GPU,

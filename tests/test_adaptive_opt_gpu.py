@@ -1,0 +1,192 @@
+"""Adam / RMSProp / Adagrad in the fused optimizer launch (misc.hip adaptive_opt_k), on the GPU:
+the kernel against a float64 oracle on a layout that hits every access path, the executors'
+wiring, hipGraph replay against eager (bitwise) and the training CLI with its checkpoint."""
+import importlib.util
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from distributed_tensorflow_ibm_mnist_amd.models import get_model, torch_ref
+from distributed_tensorflow_ibm_mnist_amd.runtime.params import FlatParams, OptConfig
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("adaptive_oracle", os.path.join(ROOT, "tests", "adaptive_oracle.py"))
+oracle = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(oracle)
+
+pytestmark = pytest.mark.gpu
+
+# offsets: a/weights 0 (odd count 175: its last pair is the scalar tail), a/biases 175 (odd
+# offset: scalar path), b/weights 182 (even: 8-byte path; 1320 = 2 blocks of 512 + 296), b/biases
+# 1502 (odd count), c/weights 1535 (odd offset AND more than one block), c/biases 2195
+SHAPES = [("a/weights", (5, 5, 1, 7), 0.0), ("a/biases", (7,), None), ("b/weights", (40, 33), 0.004),
+          ("b/biases", (33,), None), ("c/weights", (33, 20), 0.002), ("c/biases", (20,), None)]
+PADS = {"a/weights": (2, 8), "b/weights": (40, 40), "c/weights": (40, 24)}
+ZERO_GRAD = "b/biases"
+
+
+def np_of(t):
+    return t.detach().cpu().numpy()
+
+
+def check_state(fp, ref, rule, names):
+    for n in names:
+        s1, s2 = fp.slot_views(n)
+        oracle.close(np_of(fp.param_view(n)), ref.p[n])
+        oracle.close(np_of(fp.ema_view(n)), ref.ema[n])
+        oracle.close(np_of(s1), ref.s1[n])
+        if rule == "adagrad":
+            assert s2 is None
+        else:
+            oracle.close(np_of(s2), ref.s2[n])
+
+
+@pytest.mark.parametrize("rule", ["adam", "rmsprop", "adagrad"])
+def test_kernel_matches_float64_oracle(dev, K, rule):
+    torch.manual_seed(30)
+    init = {n: torch.randn(*s) for n, s, _ in SHAPES}
+    fp = FlatParams.build(SHAPES, init, dev, pads=PADS)
+    fp.enable_transposed({"b/weights": (40, 48)})
+    cfg = OptConfig(lr0=0.05, decay_rate=0.5, decay_steps=2, ema_max=0.9999, rule=rule)
+    fp.init_slots(cfg)
+    assert [int(r[0]) & 1 for r in fp.segs.tolist()] == [0, 1, 0, 0, 1, 1]
+    ref = oracle.Oracle(rule, {n: v.numpy() for n, v in init.items()}, {n: wd for n, _, wd in SHAPES},
+                        0.05, 0.5, 2, 0.9999, grad_scale=0.5)
+    for _ in range(5):
+        g = {n: torch.randn_like(init[n]) for n in init}
+        g[ZERO_GRAD].zero_()
+        for n in g:
+            fp.grad_view(n).copy_(g[n])
+        fp.apply(cfg, grad_scale=0.5)
+        fp.step.add_(1)
+        ref.step({n: v.numpy() for n, v in g.items()})
+    torch.cuda.synchronize()
+    check_state(fp, ref, rule, list(init))
+    assert torch.equal(fp.param_view(ZERO_GRAD).cpu(), init[ZERO_GRAD])   # zero gradient: no update, no NaN
+    # bf16 copies: bf16(params) in the valid region, zero in the padding
+    for n in PADS:
+        e = fp.by_name[n]
+        c = fp.bf16_view(n)
+        want = fp.param_view(n).to(torch.bfloat16)
+        assert torch.equal(c[..., :e.I, :e.J], want.view(c.shape[:-2] + (e.I, e.J))), n
+        assert c[..., e.I:, :].float().abs().sum().item() == 0 and c[..., :, e.J:].float().abs().sum().item() == 0, n
+    t = fp.bf16t_view("b/weights")
+    assert t.shape == (40, 48)
+    assert torch.equal(t[:33, :40], fp.param_view("b/weights").to(torch.bfloat16).t())
+    assert t[33:].float().abs().sum().item() == 0 and t[:, 40:].float().abs().sum().item() == 0
+
+
+def test_binding_validates_rule_and_slot2(dev, K):
+    init = {n: torch.randn(*s) for n, s, _ in SHAPES}
+    fp = FlatParams.build(SHAPES, init, dev, pads=PADS)
+    args = (fp.params, fp.grads, fp.mom, fp.ema, fp.bf16, fp.segs, fp.step, 0.1, 0.1, 0, 0.0, False, False, 1.0,
+            0.9999)
+    with pytest.raises(RuntimeError, match="needs slot2"):
+        K.fused_optimizer(*args, rule="adam")
+    with pytest.raises(RuntimeError, match="slot2"):
+        K.fused_optimizer(*args, rule="rmsprop", slot2=torch.zeros(fp.total - 1, device=dev))
+    with pytest.raises(RuntimeError, match="unknown rule"):
+        K.fused_optimizer(*args, rule="adadelta")
+    with pytest.raises(RuntimeError, match="init_slots"):
+        fp.apply(OptConfig(rule="adam"))
+    torch.cuda.synchronize()
+    assert torch.equal(fp.params.cpu(), torch.cat([init[n].reshape(-1) for n, _, _ in SHAPES]))   # nothing ran
+
+
+def _fill_batch(net, B, g, f32=False):
+    x = torch.rand(B, 28, 28, 1, device=net.device, generator=g) - 0.5
+    net.x0.copy_(x if f32 else x.to(torch.bfloat16))
+    net.labels.copy_(torch.randint(0, 10, (B,), device=net.device, generator=g, dtype=torch.int32))
+
+
+@pytest.mark.parametrize("rule,model,f32", [("adam", "lenet5", False), ("rmsprop", "mlp", True)])
+def test_executor_update_matches_oracle(dev, K, rule, model, f32):
+    from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet
+    from distributed_tensorflow_ibm_mnist_amd.runtime.executor_f32 import HipNetF32
+    B = 128
+    spec = get_model(model, 1)
+    cfg = OptConfig(lr0=0.01, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule=rule)
+    net = (HipNetF32 if f32 else HipNet)(spec, B, dev, torch_ref.init_params(spec, seed=3), cfg)
+    fp = net.fp
+    g = torch.Generator(device=dev).manual_seed(3)
+    for _ in range(2):          # the second step starts from non-trivial slots and t = 2
+        _fill_batch(net, B, g, f32)
+        net.forward(defer_head=True)
+        net.loss_and_grad()
+        net.backward()
+        torch.cuda.synchronize()
+        step = int(fp.step.item())
+        names = fp.names()
+        ref = oracle.Oracle(rule, {n: np_of(fp.param_view(n)) for n in names},
+                            {e.name: e.wd for e in fp.entries}, 0.01, 0.1, 0, 0.9999, step0=step)
+        for n in names:
+            s1, s2 = fp.slot_views(n)
+            ref.s1[n] = np_of(s1).astype(np.float64)
+            ref.s2[n] = np_of(s2).astype(np.float64)
+            ref.ema[n] = np_of(fp.ema_view(n)).astype(np.float64)
+        grads = {n: np_of(fp.grad_view(n)).copy() for n in names}
+        net.update()
+        torch.cuda.synchronize()
+        ref.step(grads)
+        check_state(fp, ref, rule, names)
+        assert int(fp.step.item()) == step + 1
+    assert net.read_stats()["nan"] == 0.0
+
+
+def test_graph_replay_equals_eager_bitwise(dev, K):
+    from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet
+    from distributed_tensorflow_ibm_mnist_amd.runtime.graph import StepGraph
+    B, steps = 128, 4
+    spec = get_model("lenet5", 1)
+    g = torch.Generator(device=dev).manual_seed(8)
+    xs = [(torch.rand(B, 28, 28, 1, device=dev, generator=g) - 0.5).to(torch.bfloat16) for _ in range(steps)]
+    ys = [torch.randint(0, 10, (B,), device=dev, generator=g, dtype=torch.int32) for _ in range(steps)]
+    out = []
+    for graph in (False, True):
+        net = HipNet(spec, B, dev, torch_ref.init_params(spec, seed=8),
+                     OptConfig(lr0=0.002, ema_max=0.9999, rule="adam"))
+        sg = None
+        for k in range(steps):
+            net.x0.copy_(xs[k])
+            net.labels.copy_(ys[k])
+            if not graph:
+                net.train_step()
+            elif sg is None:
+                sg = StepGraph(net.train_step, warmup=1)    # the warm-up is step 0; capture executes nothing
+            else:
+                sg.replay()
+        torch.cuda.synchronize()
+        assert int(net.fp.step.item()) == steps
+        out.append([t.clone() for t in (net.fp.params, net.fp.mom, net.fp.slot2, net.fp.ema)])
+    for a, b, name in zip(out[0], out[1], ("params", "m", "v", "ema")):
+        assert torch.equal(a, b), name
+    assert out[0][2].abs().max().item() > 0
+
+
+def test_cli_adam_trains_and_checkpoints(tmp_path, dev):
+    d = str(tmp_path / "adam")
+    args = ["--model=lenet5", "--in_channels=1", "--optimizer=adam", "--base_lr=0.001", "--batch_size=128",
+            "--max_steps=40", "--test_interval=1000", "--log_step_count_steps=0", "--save_summaries_steps=1",
+            "--train_data=synthetic://4000", "--test_data=synthetic://512?seed=1", "--eval_examples=256",
+            f"--train_dir={d}"]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py")] + args, cwd=ROOT, capture_output=True,
+                       text=True, timeout=180, env=dict(os.environ, PYTHONUNBUFFERED="1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    from distributed_tensorflow_ibm_mnist_amd.ckpt.saver import Saver
+    t = Saver.restore(os.path.join(d, "model.ckpt-40"))
+    for k in ("conv1/weights/Adam", "conv1/weights/Adam_1", "beta1_power", "beta2_power", "global_step"):
+        assert k in t, k
+    assert int(t["global_step"]) == 40
+    # the session's per-step cross_entropy scalars (train_dir events)
+    from distributed_tensorflow_ibm_mnist_amd.obs.events import find_event_files, read_events
+    ce = {}
+    for f in find_event_files(d):
+        for ev in read_events(f):
+            if "cross_entropy" in ev["values"]:
+                ce[ev["step"]] = ev["values"]["cross_entropy"]
+    print(f"adam lenet5 B=128: cross_entropy step 1 = {ce[1]:.4f}, step 40 = {ce[40]:.4f}")
+    assert ce[40] < ce[1], (ce[1], ce[40])
