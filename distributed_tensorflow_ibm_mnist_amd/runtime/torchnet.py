@@ -70,6 +70,13 @@ def torch_update(fp: FlatParams, cfg: OptConfig, grad_scale: float = 1.0) -> Non
             fp.ema.sub_((1.0 - d) * (fp.ema - fp.params))
 
 
+def _in_top1(logits: torch.Tensor, lab: torch.Tensor) -> torch.Tensor:
+    """Top-1 count with the reference's tf.nn.in_top_k rule (mnist_input.py:237-243), which is
+    also the HIP kernels': a row is correct when logit[label] >= max(logits), so a tie at the
+    maximum counts for every tied class (argmax would credit only the first)."""
+    return (logits.gather(1, lab.view(-1, 1)).squeeze(1) >= logits.max(1).values).sum().float()
+
+
 class TorchNet:
     def __init__(self, spec: ModelSpec, batch: int, device, init: Dict[str, torch.Tensor],
                  opt: Optional[OptConfig] = None, autocast: Optional[bool] = None):
@@ -123,7 +130,7 @@ class TorchNet:
         loss = F.cross_entropy(self._logits, lab, reduction="sum")
         with torch.no_grad():
             self.stats[0] += loss.detach()
-            self.stats[1] += (self._logits.argmax(1) == lab).sum().float()
+            self.stats[1] += _in_top1(self._logits, lab)
             if not torch.isfinite(loss.detach()):
                 self.stats[2] = 1.0
         self._loss = loss * ((1.0 / nb) if scale is None else scale)
@@ -176,7 +183,7 @@ class TorchNet:
             logits = self.forward(nb, grad=False)
             lab = self.labels[:nb].long()
             st[0] += F.cross_entropy(logits, lab, reduction="sum")
-            st[1] += (logits.argmax(1) == lab).sum().float()
+            st[1] += _in_top1(logits, lab)
         return st
 
     def probs(self, nb: int) -> torch.Tensor:

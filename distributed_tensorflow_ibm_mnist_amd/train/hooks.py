@@ -77,7 +77,14 @@ class NanTensorHook(SessionRunHook):
     softmax-CE / finalize kernels and never cleared, so no step is missed) is copied to
     a pinned host mirror with a non-blocking copy every ``every_n_steps`` steps and
     checked one step later -- a NaN at step k is raised by step k + N, with one host
-    sync per N steps instead of per step.  ``end`` does a final synchronous check."""
+    sync per N steps instead of per step.  ``end`` does a final synchronous check.
+
+    What the flag guarantees on the HIP path: a non-finite cross-entropy (any row of the batch)
+    or a non-finite total loss (cross-entropy + weight-decay terms) of a step sets it.  A NaN
+    elsewhere is NOT guaranteed to: every ReLU in the kernels is ``fmaxf(v, 0.f)`` and the pools
+    are ``v_max``, which turn a NaN into 0, so a NaN pixel or a NaN weight ahead of a ReLU never
+    reaches the loss (such a weight is still caught through its sum(w^2) term when it is a
+    weight-decay entry, coefficient 0.0 included).  tests/test_stats_path_gpu.py pins both."""
 
     def __init__(self, fail_on_nan_loss: bool = True, every_n_steps: int = 1, log=print):
         self.fail, self.every = fail_on_nan_loss, max(1, every_n_steps)

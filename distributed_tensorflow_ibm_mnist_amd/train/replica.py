@@ -173,6 +173,11 @@ class Replica:
         return {"loss": v[0], "accuracy": v[1]}
 
     def inject_nan(self) -> None:
+        """Fault injection: poison params[0], the first layer's first weight.  On the torch path
+        the NaN propagates to the loss; on the HIP path the layer's fmaxf ReLU turns it into 0,
+        and the NaN guard fires through the weight-decay term alone -- the weight is a
+        weight-decay entry (coefficient 0.0 included), so the step's total loss is
+        ce + wd / 2 * sum(w^2) = NaN (tests/test_stats_path_gpu.py, total-loss route)."""
         with torch.no_grad():
             self.net.fp.params[0] = float("nan")
         self.net.fp.refresh_bf16()

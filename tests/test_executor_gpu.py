@@ -300,10 +300,12 @@ def test_refcnn_lrn1_backward_fold(dev, K, cin, monkeypatch):
         assert net.fold_lrn == (fold == "1") and net.fold_lrn_fwd == (fold == "1")
         net.x0.copy_(x)
         net.labels.copy_(y)
-        logits = net.forward(defer_head=True).clone()
+        net.forward(defer_head=True)
         net.loss_and_grad()
+        logits = net.logits.clone()     # the ce_tail head writes them in loss_and_grad
         net.backward()
         torch.cuda.synchronize()
+        assert logits.abs().max() > 0
         return {"logits": logits, **{n: net.fp.grad_view(n).clone() for n in init}}
 
     ref, fold = grads("0"), grads("1")

@@ -128,10 +128,12 @@ def test_refcnn_norm1_forward_fold_step(dev, K, cin, monkeypatch):
         assert net.fold_lrn_fwd1 == (fold == "1")
         net.x0.copy_(x)
         net.labels.copy_(y)
-        logits = net.forward(defer_head=True).clone()
+        net.forward(defer_head=True)
         net.loss_and_grad()
+        logits = net.logits.clone()     # the ce_tail head writes them in loss_and_grad
         net.backward()
         torch.cuda.synchronize()
+        assert logits.abs().max() > 0
         return {"logits": logits, "norm1": net.activation("norm1").clone(),
                 **{n: net.fp.grad_view(n).clone() for n in init}}
 

@@ -137,3 +137,26 @@ def test_inference_cli_after_training(tmp_path):
     res = json.load(open(tmp_path / "val.json"))
     assert res["summary"]["count"] == 40 and res["summary"]["accuracy"] > 0.3
     assert os.path.exists(tmp_path / "val.csv")
+
+
+def test_torchnet_counts_ties_like_in_top_k():
+    """--impl torch is the functional baseline of the HIP kernels, which count a row as correct
+    when logit[label] >= max (tf.nn.in_top_k, mnist_input.py:237-243): with a zeroed last layer
+    the logits are the bias, whose two equal maxima (classes 2 and 7) both count, and on a dead
+    network (every class equal) every label does.  argmax would credit class 2 alone."""
+    import torch
+    from distributed_tensorflow_ibm_mnist_amd.models import get_model, torch_ref
+    from distributed_tensorflow_ibm_mnist_amd.runtime.torchnet import TorchNet
+    spec = get_model("mlp", 1)
+    labels = (torch.arange(20) % 10).to(torch.int32)
+    for bias, want in [([0.1, 0.2, 1.5, 0.3, -1.0, 0.0, 0.4, 1.5, 0.2, -0.3], 4.0), ([0.25] * 10, 20.0)]:
+        init = torch_ref.init_params(spec, seed=0)
+        init["softmax_linear/weights"].zero_()
+        init["softmax_linear/biases"] = torch.tensor(bias)
+        net = TorchNet(spec, 20, "cpu", init)
+        net.x0.copy_(torch.rand(net.x0.shape, generator=torch.Generator().manual_seed(1)) - 0.5)
+        net.labels.copy_(labels)
+        assert net.eval_batch(20, torch.zeros(8))[1].item() == want
+        net.forward()
+        net.loss_and_grad()
+        assert net.stats[1].item() == want
