@@ -11,7 +11,11 @@ writes params, EMA, the slots and (weights) a bf16 copy:
     adagrad           as momentum: one slot                = 30 B
     sgd               3 reads + 2 writes of 4 B + 2 B bf16 = 22 B
 
-    python bench/micro_opt.py [--launches 200] [--rounds 5] [--model reference_cnn]
+--clip_norm C times every rule a second time with clipping by global norm ("<rule>+clip": the
+reduction launch, 8 B per element read, then the clipped optimizer launch), interleaved with the
+plain launches; C is large by default so the updates themselves stay the same.
+
+    python bench/micro_opt.py [--launches 200] [--rounds 5] [--model reference_cnn] [--clip_norm 1e30]
 prints one JSON line.
 """
 import argparse
@@ -24,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 BYTES = {"sgd": 22, "momentum": 30, "adam": 38, "rmsprop": 38, "adagrad": 30}
+CLIP_BYTES = 8   # the reduction reads params and grads once more
 
 
 def main() -> int:
@@ -34,6 +39,7 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--rules", default="momentum,adam,rmsprop,adagrad")
+    ap.add_argument("--clip_norm", type=float, default=None, help="also time each rule with this clip_norm")
     args = ap.parse_args()
 
     import torch
@@ -47,17 +53,20 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     spec = get_model(args.model, args.in_channels)
     init = init_params(spec, seed=0)
-    rules = [r for r in args.rules.split(",") if r]
+    base_rules = [r for r in args.rules.split(",") if r]
+    rules = base_rules + ([r + "+clip" for r in base_rules] if args.clip_norm else [])
     nets = {}
-    for r in rules:
+    for key in rules:
+        r, clip = key.split("+")[0], (args.clip_norm if key.endswith("+clip") else None)
         if r in ("adam", "rmsprop", "adagrad"):
-            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r)
+            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r, clip_norm=clip)
         else:
-            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, momentum=0.9 if r != "sgd" else 0.0, use_momentum=r != "sgd")
+            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, momentum=0.9 if r != "sgd" else 0.0, use_momentum=r != "sgd",
+                            clip_norm=clip)
         net = HipNet(spec, 16, dev, init, cfg)      # the executor's own FlatParams layout (pads, W^T copies)
         net.fp.grads.copy_(torch.randn(net.fp.total, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
                            * 1e-2)
-        nets[r] = net
+        nets[key] = net
     n = nets[rules[0]].fp.total
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     times = {r: [] for r in rules}
@@ -80,14 +89,23 @@ def main() -> int:
            "rules": {}}
     for r in rules:
         med = statistics.median(times[r])
+        nbytes = BYTES[r.split("+")[0]] + (CLIP_BYTES if r.endswith("+clip") else 0)
         out["rules"][r] = {"us_median": round(med, 2), "us_min": round(min(times[r]), 2),
-                           "us_all": [round(t, 2) for t in times[r]], "bytes_per_element": BYTES[r],
-                           "GBps": round(n * BYTES[r] / med / 1e3, 1)}
+                           "us_all": [round(t, 2) for t in times[r]], "bytes_per_element": nbytes,
+                           "GBps": round(n * nbytes / med / 1e3, 1)}
     if "momentum" in out["rules"]:
         base = out["rules"]["momentum"]["us_median"]
         for r in rules:
             out["rules"][r]["ratio_to_momentum"] = round(out["rules"][r]["us_median"] / base, 3)
-            out["rules"][r]["expected_ratio"] = round(BYTES[r] / BYTES["momentum"], 3)
+            out["rules"][r]["expected_ratio"] = round(out["rules"][r]["bytes_per_element"] / BYTES["momentum"], 3)
+    if args.clip_norm:
+        from distributed_tensorflow_ibm_mnist_amd.ops._ext import kernels
+        out["clip_norm"] = args.clip_norm
+        out["grad_norm_blocks"] = int(kernels().grad_norm_max_blocks())
+        for r in base_rules:   # clipped (two launches) over plain (one), next to the byte ratio
+            c, p = out["rules"][r + "+clip"], out["rules"][r]
+            c["ratio_to_unclipped"] = round(c["us_median"] / p["us_median"], 3)
+            c["expected_ratio_to_unclipped"] = round(c["bytes_per_element"] / p["bytes_per_element"], 3)
     print(json.dumps(out), flush=True)
     return 0
 

@@ -38,6 +38,7 @@ def parse(argv=None):
     ap.add_argument("--optimizer", default="momentum", choices=["sgd", "momentum", "nesterov", "adam", "rmsprop", "adagrad"],
                     help="adam / rmsprop / adagrad: TF1 defaults (pass a matching --lr, e.g. 0.001 for adam)")
     ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--clip_norm", type=float, default=None, help="clip the gradients by this global norm")
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
     ap.add_argument("--probe", type=int, default=10000, help="training images in the accuracy probe")
@@ -79,10 +80,12 @@ def run(args) -> dict:
             dist.init_process_group("nccl", device_id=dev)
     spec = get_model(args.model, args.in_channels)
     if args.optimizer in ("adam", "rmsprop", "adagrad"):
-        opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule=args.optimizer)
+        opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule=args.optimizer,
+                        clip_norm=args.clip_norm)
     else:
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, momentum=0.9 if args.optimizer != "sgd" else 0.0,
-                        nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999)
+                        nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999,
+                        clip_norm=args.clip_norm)
     init = init_params(spec, seed=args.seed)
     if args.impl == "hip":
         from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet

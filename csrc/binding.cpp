@@ -533,13 +533,55 @@ mnistx::FinArgs prep_fin(Tensor step, Tensor stats, optional<Tensor> l2, optiona
                          optional<Tensor> loss_ema, int64_t n_ema, int64_t batch, bool increment,
                          optional<Tensor> l2_ranges, optional<Tensor> ce_work, int64_t ce_nblk);
 
+// bf: the buffer of the bf16 copies, whose ranges are checked (nullptr: a caller that never
+// writes them); max_l2: the largest track_l2 index
+std::vector<mnistx::OptSeg> read_segs(const Tensor& segs, int64_t total, const Tensor* bf, int& max_l2) {
+  TORCH_CHECK(!segs.is_cuda() && segs.scalar_type() == at::kLong && segs.dim() == 2 && segs.size(1) == 14,
+              "segs: CPU int64 [n,14]");
+  const int nseg = (int)segs.size(0);
+  std::vector<mnistx::OptSeg> sv(nseg);
+  auto a = segs.accessor<int64_t, 2>();
+  int64_t expect_off = 0;
+  max_l2 = 0;
+  for (int i = 0; i < nseg; ++i) {
+    auto& s = sv[i];
+    s.off = a[i][0];
+    s.n = a[i][1];
+    s.G = (int)a[i][2];
+    s.I = (int)a[i][3];
+    s.J = (int)a[i][4];
+    s.Ip = (int)a[i][5];
+    s.Jp = (int)a[i][6];
+    s.bf_off = a[i][7];
+    int32_t wb = (int32_t)a[i][8];
+    std::memcpy(&s.wd, &wb, 4);
+    s.track_l2 = (int)a[i][9];
+    s.bft_off = a[i][10];
+    s.Jt = (int)a[i][11];
+    s.It = (int)a[i][12];
+    TORCH_CHECK(s.off == expect_off, "segments must tile the flat buffer in order");
+    TORCH_CHECK(s.n == (int64_t)s.G * s.I * s.J, "segment size mismatch");
+    TORCH_CHECK(s.Ip >= s.I && s.Jp >= s.J, "padding");
+    if (bf && s.bf_off >= 0)
+      TORCH_CHECK(s.bf_off + (int64_t)s.G * s.Ip * s.Jp <= bf->numel(), "bf16 copy out of range");
+    if (bf && s.bft_off >= 0) {
+      TORCH_CHECK(s.bf_off >= 0 && s.G == 1 && s.Jt >= s.J && s.It >= s.I, "transposed copy geometry");
+      TORCH_CHECK(s.bft_off + (int64_t)s.Jt * s.It <= bf->numel(), "transposed bf16 copy out of range");
+    }
+    if (s.track_l2 > max_l2) max_l2 = s.track_l2;
+    expect_off += s.n;
+  }
+  TORCH_CHECK(expect_off == total, "segments do not cover the parameters");
+  return sv;
+}
+
 void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor bf, Tensor segs, Tensor step,
                      double lr0, double decay_rate, int64_t decay_steps, double momentum, bool nesterov,
                      bool use_momentum, double grad_scale, double ema_max, optional<Tensor> l2,
                      optional<Tensor> guard, int64_t guard_want, optional<Tensor> guard_err, int64_t guard_id,
                      optional<py::tuple> fin, optional<py::tuple> perm, const std::string& rule,
                      optional<Tensor> slot2, double beta1, double beta2, optional<double> epsilon,
-                     double rmsprop_decay) {
+                     double rmsprop_decay, optional<double> clip_norm, optional<Tensor> gnorm) {
   const int64_t total = params.numel();
   check(params, at::kFloat, total, "params");
   check(grads, at::kFloat, total, "grads");
@@ -563,42 +605,9 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
   if (rule_id == mnistx::OPT_RMSPROP) TORCH_CHECK(rmsprop_decay >= 0 && rmsprop_decay <= 1, "rmsprop: decay in [0, 1]");
   if (ema_max >= 0) check(ema, at::kFloat, total, "ema");
   check(step, at::kLong, 1, "step");
-  TORCH_CHECK(!segs.is_cuda() && segs.scalar_type() == at::kLong && segs.dim() == 2 && segs.size(1) == 14,
-              "segs: CPU int64 [n,14]");
-  const int nseg = (int)segs.size(0);
-  std::vector<mnistx::OptSeg> sv(nseg);
-  auto a = segs.accessor<int64_t, 2>();
-  int64_t expect_off = 0;
   int max_l2 = 0;
-  for (int i = 0; i < nseg; ++i) {
-    auto& s = sv[i];
-    s.off = a[i][0];
-    s.n = a[i][1];
-    s.G = (int)a[i][2];
-    s.I = (int)a[i][3];
-    s.J = (int)a[i][4];
-    s.Ip = (int)a[i][5];
-    s.Jp = (int)a[i][6];
-    s.bf_off = a[i][7];
-    int32_t wb = (int32_t)a[i][8];
-    std::memcpy(&s.wd, &wb, 4);
-    s.track_l2 = (int)a[i][9];
-    s.bft_off = a[i][10];
-    s.Jt = (int)a[i][11];
-    s.It = (int)a[i][12];
-    TORCH_CHECK(s.off == expect_off, "segments must tile the flat buffer in order");
-    TORCH_CHECK(s.n == (int64_t)s.G * s.I * s.J, "segment size mismatch");
-    TORCH_CHECK(s.Ip >= s.I && s.Jp >= s.J, "padding");
-    if (s.bf_off >= 0)
-      TORCH_CHECK(s.bf_off + (int64_t)s.G * s.Ip * s.Jp <= bf.numel(), "bf16 copy out of range");
-    if (s.bft_off >= 0) {
-      TORCH_CHECK(s.bf_off >= 0 && s.G == 1 && s.Jt >= s.J && s.It >= s.I, "transposed copy geometry");
-      TORCH_CHECK(s.bft_off + (int64_t)s.Jt * s.It <= bf.numel(), "transposed bf16 copy out of range");
-    }
-    if (s.track_l2 > max_l2) max_l2 = s.track_l2;
-    expect_off += s.n;
-  }
-  TORCH_CHECK(expect_off == total, "segments do not cover the parameters");
+  const std::vector<mnistx::OptSeg> sv = read_segs(segs, total, &bf, max_l2);
+  const int nseg = (int)sv.size();
   check(bf, at::kBFloat16, 0, "bf");
   float* l2p = nullptr;
   const int l2n = max_l2;
@@ -641,6 +650,20 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
     op.guard_err = P<int>(*guard_err);
     op.guard_id = (int)guard_id;
   }
+  // clipping by global norm: gnorm = [norm, scale, grad_norm_max_blocks() partials]
+  float clip = 0.f;
+  float* gnp = nullptr;
+  if (clip_norm.has_value()) {
+    TORCH_CHECK(std::isfinite(*clip_norm) && *clip_norm > 0 && (float)*clip_norm > 0.f &&
+                    std::isfinite((float)*clip_norm), "fused_optimizer: clip_norm must be finite and > 0");
+    TORCH_CHECK(gnorm.has_value() && gnorm->defined(), "fused_optimizer: clip_norm needs gnorm");
+    TORCH_CHECK(!(guard.has_value() && guard->defined()),
+                "fused_optimizer: clip_norm cannot be combined with a push guard (parameter-server mode)");
+    check(*gnorm, at::kFloat, 2 + mnistx::grad_norm_max_blocks(), "gnorm");
+    TORCH_CHECK(gnorm->device() == params.device(), "gnorm: on the parameters' device");
+    clip = (float)*clip_norm;
+    gnp = P<float>(*gnorm);
+  }
   // fin: finalize_step's arguments after `step` (the same step tensor), run in this launch
   mnistx::FinArgs fa{};
   const bool has_fin = fin.has_value() && !fin->is_none();
@@ -680,8 +703,24 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
                                  (use_momentum || adaptive) ? P<float>(mom) : nullptr,
                                  ema_max >= 0 ? P<float>(ema) : nullptr, BFm(bf), sv.data(), nseg, total,
                                  P<const int64_t>(step), op, l2p, l2n, cur_stream(), has_fin ? &fa : nullptr,
-                                 has_perm ? &pj : nullptr, two_slots ? P<float>(*slot2) : nullptr),
+                                 has_perm ? &pj : nullptr, two_slots ? P<float>(*slot2) : nullptr, clip, gnp),
          "fused_optimizer");
+}
+
+// The global norm of g_eff = grad * grad_scale + wd * p alone, as the clipped update computes it:
+// gnorm[0] afterwards (gnorm[2..]: the per-block partials).  Not on the training path.
+void grad_global_norm(Tensor params, Tensor grads, Tensor segs, double grad_scale, Tensor gnorm) {
+  const int64_t total = params.numel();
+  check(params, at::kFloat, total, "params");
+  check(grads, at::kFloat, total, "grads");
+  check(gnorm, at::kFloat, 2 + mnistx::grad_norm_max_blocks(), "gnorm");
+  TORCH_CHECK(grads.device() == params.device() && gnorm.device() == params.device(),
+              "grads / gnorm: on the parameters' device");
+  int max_l2 = 0;
+  const std::vector<mnistx::OptSeg> sv = read_segs(segs, total, nullptr, max_l2);
+  hip_ok(mnistx::grad_global_norm(P<const float>(params), P<const float>(grads), sv.data(), (int)sv.size(),
+                                  (float)grad_scale, P<float>(gnorm), cur_stream()),
+         "grad_global_norm");
 }
 
 mnistx::FinArgs prep_fin(Tensor step, Tensor stats, optional<Tensor> l2, optional<Tensor> wds, int64_t nw,
@@ -1395,7 +1434,12 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("guard_want") = 0, py::arg("guard_err") = py::none(), py::arg("guard_id") = 0,
         py::arg("fin") = py::none(), py::arg("perm") = py::none(), py::kw_only(), py::arg("rule") = "sgd",
         py::arg("slot2") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
-        py::arg("epsilon") = py::none(), py::arg("rmsprop_decay") = 0.9);
+        py::arg("epsilon") = py::none(), py::arg("rmsprop_decay") = 0.9, py::arg("clip_norm") = py::none(),
+        py::arg("gnorm") = py::none());
+  m.def("grad_global_norm", &grad_global_norm, py::arg("params"), py::arg("grads"), py::arg("segs"),
+        py::arg("grad_scale"), py::arg("gnorm"),
+        "gnorm[0] = sqrt(sum over all segments of (grad * grad_scale + wd * p)^2), fixed-order sums");
+  m.def("grad_norm_max_blocks", []() { return (int64_t)mnistx::grad_norm_max_blocks(); });
   m.def("set_opt_fin_fused", [](int64_t on) { mnistx::set_opt_fin_fused((int)on); },
         "A/B switch of the optimizer launch running the step's finalize (MNISTX_OPT_FIN_FUSED)");
   m.def("opt_fin_fused_enabled", []() { return mnistx::opt_fin_fused_enabled() != 0; });

@@ -1,6 +1,11 @@
-// The body of fused_opt_k and adaptive_opt_k<RULE> (misc.hip), included inside both kernels so
-// that each compiles it as its own code, with the kernel's parameters in scope:
-//   params, grads, mom, slot2, ema, bf, tab, step_p, op, l2, fin, pj, and `constexpr int RULE`.
+// The body of fused_opt_k, adaptive_opt_k<RULE> and clipped_opt_k<RULE> (misc.hip), included
+// inside each kernel so that each compiles it as its own code, with the kernel's parameters in scope:
+//   params, grads, mom, slot2, ema, bf, tab, step_p, op, l2, fin, pj, gnorm, clip_norm, and
+//   `constexpr int RULE`, `constexpr bool CLIP`.
+// CLIP (clipped_opt_k only): clip by global norm.  gnorm[2 ..] holds grad_sqnorm_k's per-block
+// partials of sum(g_eff^2); every block sums them itself in the same fixed order (gn_total), so
+// all blocks hold the bitwise-same norm and scale s = clip_norm / max(norm, clip_norm) with no
+// hand-off between blocks, and the rule sees g_eff * s.  Without CLIP none of it is compiled.
 // RULE = OPT_CLASSIC is SGD / momentum / Nesterov, chosen at run time by OptParams; the adaptive
 // rules (Adam, RMSProp, Adagrad) are compile-time, so the classic kernel's code does not change
 // with them.  slot2: the second slot buffer (Adam v, RMSProp ms), read and written like mom.
@@ -72,6 +77,16 @@
   // Adam's bias corrections, once per block (thread 0, behind the loads already in flight):
   // sqrt(1 - b2^t) / (1 - b1^t) with t = step + 1, as -expm1(t log b) in double -- fp32
   // 1 - powf(0.999, t) is off by 6e-5 at t = 1
+  float clip_s = 1.f;
+  if constexpr (CLIP) {   // behind the loads already in flight
+    __shared__ float gred[TPB / 64];
+    const float gn = gn_total(gnorm, gred);
+    clip_s = clip_scale(gn, clip_norm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      gnorm[0] = gn;
+      gnorm[1] = clip_s;
+    }
+  }
   float lr_t = lr;
   if constexpr (RULE == OPT_ADAM) {
     __shared__ float corr;
@@ -87,7 +102,15 @@
   for (int u = 0; u < OPT_EPT; ++u) {
     float p = pv[u];
     if (li0 + u < sg.n) sq += p * p;
-    const float g = gv[u] * op.grad_scale + sg.wd * p;
+    float g;
+    if constexpr (CLIP) {
+      // the sum as the unclipped kernels contract it (the gradient's product rounded, the decay's
+      // fused), spelled out: left to itself the compiler pairs the two products here and adds
+      // them unfused.  Then the scale: s = 1 changes no bit (tests/test_clip_norm_gpu.py).
+      g = clip_mul(__builtin_fmaf(sg.wd, p, gv[u] * op.grad_scale), clip_s);
+    } else {
+      g = gv[u] * op.grad_scale + sg.wd * p;
+    }
     so[u] = 0.f;
     if constexpr (RULE == OPT_ADAM) {
       // eps outside the root: m = v = 0 (a gradient that was always zero) gives 0 * 1/eps = 0

@@ -401,7 +401,19 @@ struct PermJob {
 // slot2: the second slot buffer, needed by op.rule = OPT_ADAM / OPT_RMSPROP (which also need mom)
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
                            int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n, hipStream_t st,
-                           const FinArgs* fin = nullptr, const PermJob* perm = nullptr, float* slot2 = nullptr);
+                           const FinArgs* fin = nullptr, const PermJob* perm = nullptr, float* slot2 = nullptr,
+                           float clip_norm = 0.f, float* gnorm = nullptr);
+// Clipping by global norm (clip_norm > 0; tf.clip_by_global_norm): two launches on st, eagerly
+// and under capture alike -- grad_sqnorm_k reduces sum(g_eff^2), g_eff = grad * grad_scale + wd * p
+// over ALL segments, into grad_norm_max_blocks() per-block partials in a fixed order, then the
+// rule's clipped_opt_k, each block of which sums the partials itself and applies
+// s = clip_norm / max(norm, clip_norm) (a non-finite norm: s = NaN) to g_eff.
+// gnorm (2 + grad_norm_max_blocks() floats): [0] the norm before clipping  [1] s  [2..] partials.
+// Invalid together with a PS push guard.
+int grad_norm_max_blocks();
+// the reduction alone: gnorm[0] = the global norm, by the same fixed-order sums
+hipError_t grad_global_norm(const float* params, const float* grads, const OptSeg* segs, int nseg, float grad_scale,
+                            float* gnorm, hipStream_t st);
 void set_opt_fin_fused(int on);
 int opt_fin_fused_enabled();
 // l2r (optional, device int32 [nw][3] = {weight index, first block, end block}): sum the

@@ -894,13 +894,52 @@ struct SegTable {
   int l2n;                           // l2[0..l2n): per-tensor sums; l2[l2n + block]: partials
 };
 
+// Clipping by global norm: the pieces fused_opt_body.h uses under CLIP (kernels further down).
+constexpr int GN_BLOCKS = 512;   // grid of grad_sqnorm_k = partials every optimizer block sums
+constexpr int GN_UNROLL = 4;     // full chunks whose loads grad_sqnorm_k issues together
+static_assert(GN_BLOCKS <= 1024 && GN_BLOCKS % TPB == 0, "gn_total: GN_BLOCKS / TPB partials per thread");
+// sqrt of the sum of the GN_BLOCKS partials gnorm[2 ..], the same bits in every thread of every
+// block that calls it: thread t adds partials t, t + TPB, ... in order, then warp_sum, then the
+// waves in index order.  gred: TPB / 64 floats of LDS.  Contains a __syncthreads.
+DEV float gn_total(const float* gnorm, float* gred) {
+  constexpr int R = GN_BLOCKS / TPB;
+  float v[R];
+#pragma unroll
+  for (int u = 0; u < R; ++u) v[u] = gnorm[2 + threadIdx.x + u * TPB];
+  float t = 0.f;
+#pragma unroll
+  for (int u = 0; u < R; ++u) t += v[u];
+  t = warp_sum(t);
+  if ((threadIdx.x & 63) == 0) gred[threadIdx.x >> 6] = t;
+  __syncthreads();
+  float ss = 0.f;
+#pragma unroll
+  for (int w = 0; w < TPB / 64; ++w) ss += gred[w];
+  return sqrtf(ss);
+}
+// s = c / max(gn, c): exactly 1 for gn <= c (gn = 0 included); NaN for a non-finite gn, as
+// tf.clip_by_global_norm (fmaxf would return c for a NaN norm and hide it)
+DEV float clip_scale(float gn, float c) {
+  if (!isfinite(gn)) return __builtin_nanf("");
+  return c / (gn <= c ? c : gn);
+}
+// g * s as a multiply of its own: kept out of the rule's fused multiply-adds, so that s = 1
+// leaves every rule bitwise what it is without clipping
+DEV float clip_mul(float g, float s) {
+#pragma clang fp contract(off)
+  return g * s;
+}
+
 __global__ __launch_bounds__(TPB) void fused_opt_k(float* __restrict__ params, const float* __restrict__ grads,
                                                    float* __restrict__ mom, float* __restrict__ ema,
                                                    bf16_t* __restrict__ bf, SegTable tab,
                                                    const int64_t* __restrict__ step_p, OptParams op,
                                                    float* __restrict__ l2, FinArgs fin, PermJob pj) {
   constexpr int RULE = OPT_CLASSIC;   // SGD / momentum / Nesterov, chosen at run time by OptParams
+  constexpr bool CLIP = false;
   float* const slot2 = nullptr;
+  float* const gnorm = nullptr;
+  const float clip_norm = 0.f;
 #include "fused_opt_body.h"
 }
 
@@ -912,6 +951,111 @@ __global__ __launch_bounds__(TPB) void adaptive_opt_k(float* __restrict__ params
                                                       float* __restrict__ ema, bf16_t* __restrict__ bf, SegTable tab,
                                                       const int64_t* __restrict__ step_p, OptParams op,
                                                       float* __restrict__ l2, FinArgs fin, PermJob pj) {
+  constexpr bool CLIP = false;
+  float* const gnorm = nullptr;
+  const float clip_norm = 0.f;
+#include "fused_opt_body.h"
+}
+
+// Clipping by global norm (tf.clip_by_global_norm of the gradient the rules consume,
+// g_eff = grad * grad_scale + wd * p, over ALL segments): grad_sqnorm_k, then clipped_opt_k<RULE>
+// on the same stream.  gnorm: [0] global norm  [1] scale s  [2 + b] block b's sum(g_eff^2).
+// Every sum runs in a fixed order and nothing is handed over between blocks of one launch: no
+// atomics, no ticket (red_tickets cannot be taken under capture, and one ticket address
+// serialises a large grid), so replay is bitwise equal to eager at any size.
+//
+// Block b of the GN_BLOCKS-block grid owns chunks [b * per, (b + 1) * per) of the optimizer's
+// own (segment, OPT_CHUNK) decomposition and walks them in order; a block past the last chunk
+// stores 0.  Runs of GN_UNROLL full chunks of a segment at an even offset issue all their
+// 8-byte loads before the first use; every other chunk goes through the optimizer body's pair /
+// scalar-tail paths, one at a time.  Each thread adds its elements in chunk order.
+DEV float gn_term(float acc, float p, float g, float grad_scale, float wd) {
+  const float ge = g * grad_scale + wd * p;
+  return acc + ge * ge;
+}
+
+__global__ __launch_bounds__(TPB) void grad_sqnorm_k(const float* __restrict__ params, const float* __restrict__ grads,
+                                                     SegTable tab, float grad_scale, int per,
+                                                     float* __restrict__ gnorm) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  __shared__ float red[TPB / 64];
+  const int nc = tab.blk0[tab.n];
+  const int c0 = min(nc, (int)blockIdx.x * per), c1 = min(nc, c0 + per);
+  float acc = 0.f;
+  int si = 0, c = c0;
+  while (c < c1) {
+    while (si + 1 < tab.n && c >= tab.blk0[si + 1]) ++si;
+    const int64_t off = tab.s[si].off, n = tab.s[si].n;
+    const float wd = tab.s[si].wd;
+    const int64_t lo = (int64_t)(c - tab.blk0[si]) * OPT_CHUNK;
+    const bool even = (off & 1) == 0;
+    if (even && c + GN_UNROLL <= c1 && lo + GN_UNROLL * OPT_CHUNK <= n) {
+      const int64_t e = off + lo + 2 * (int64_t)threadIdx.x;
+      f32x2_t p2[GN_UNROLL], g2[GN_UNROLL];
+#pragma unroll
+      for (int u = 0; u < GN_UNROLL; ++u) {
+        p2[u] = *(const f32x2_t*)(params + e + u * OPT_CHUNK);
+        g2[u] = *(const f32x2_t*)(grads + e + u * OPT_CHUNK);
+      }
+#pragma unroll
+      for (int u = 0; u < GN_UNROLL; ++u) {
+        acc = gn_term(acc, p2[u][0], g2[u][0], grad_scale, wd);
+        acc = gn_term(acc, p2[u][1], g2[u][1], grad_scale, wd);
+      }
+      c += GN_UNROLL;
+      continue;
+    }
+    // out-of-range elements load element 0 and are never added
+    const int64_t li0 = lo + 2 * (int64_t)threadIdx.x;
+    float pv[OPT_EPT], gv[OPT_EPT];
+    if (even && li0 + 1 < n) {
+      const f32x2_t p2 = *(const f32x2_t*)(params + off + li0), g2 = *(const f32x2_t*)(grads + off + li0);
+#pragma unroll
+      for (int u = 0; u < OPT_EPT; ++u) {
+        pv[u] = p2[u];
+        gv[u] = g2[u];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < OPT_EPT; ++u) {
+        const int64_t li = li0 + u;
+        const int64_t e = off + (li < n ? li : 0);
+        pv[u] = params[e];
+        gv[u] = grads[e];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < OPT_EPT; ++u)
+      if (li0 + u < n) acc = gn_term(acc, pv[u], gv[u], grad_scale, wd);
+    ++c;
+  }
+  acc = warp_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int w = 0; w < TPB / 64; ++w) t += red[w];
+    gnorm[2 + blockIdx.x] = t;
+  }
+}
+
+// grad_global_norm's last step (not on the training path, where every optimizer block does this)
+__global__ __launch_bounds__(TPB) void gnorm_finish_k(float* __restrict__ gnorm) {
+  __shared__ float gred[TPB / 64];
+  const float gn = gn_total(gnorm, gred);
+  if (threadIdx.x == 0) gnorm[0] = gn;
+}
+
+// the optimizer body compiled with clipping, one instance per rule (slot2: as adaptive_opt_k;
+// unused by OPT_CLASSIC)
+template <int RULE>
+__global__ __launch_bounds__(TPB) void clipped_opt_k(float* __restrict__ params, const float* __restrict__ grads,
+                                                     float* __restrict__ mom, float* __restrict__ slot2,
+                                                     float* __restrict__ ema, bf16_t* __restrict__ bf, SegTable tab,
+                                                     const int64_t* __restrict__ step_p, OptParams op,
+                                                     float* __restrict__ l2, FinArgs fin, PermJob pj,
+                                                     float* __restrict__ gnorm, float clip_norm) {
+  constexpr bool CLIP = true;
 #include "fused_opt_body.h"
 }
 
@@ -1343,17 +1487,12 @@ hipError_t finalize_step(const FinArgs& f, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
-                           int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n,
-                           hipStream_t st, const FinArgs* fin, const PermJob* perm, float* slot2) {
-  if (nseg > MAXSEG || nseg < 1) return hipErrorInvalidValue;
-  if (op.rule < OPT_CLASSIC || op.rule > OPT_ADAGRAD) return hipErrorInvalidValue;
-  if (op.rule != OPT_CLASSIC && (!mom || (op.rule != OPT_ADAGRAD && !slot2))) return hipErrorInvalidValue;
-  if (fin && fin->nw > FIN_MAXW) return hipErrorInvalidValue;
-  SegTable tab;
+// the block -> segment table of the optimizer launches; returns the number of optimizer blocks
+// (chunks), or -1 for segments the kernels' 32-bit index math cannot hold
+static int build_seg_table(const OptSeg* segs, int nseg, int l2n, SegTable& tab) {
   int nb = 0;
   for (int i = 0; i < nseg; ++i) {
-    if (segs[i].n >= (1ll << 31) || (int64_t)segs[i].I * segs[i].J >= (1ll << 31)) return hipErrorInvalidValue;
+    if (segs[i].n >= (1ll << 31) || (int64_t)segs[i].I * segs[i].J >= (1ll << 31)) return -1;
     tab.s[i] = segs[i];
     tab.fij[i] = FastDiv((uint32_t)(segs[i].I * segs[i].J));
     tab.fj[i] = FastDiv((uint32_t)segs[i].J);
@@ -1363,6 +1502,41 @@ hipError_t fused_optimizer(float* params, const float* grads, float* mom, float*
   tab.blk0[nseg] = nb;
   tab.n = nseg;
   tab.l2n = l2n;
+  return nb;
+}
+
+int grad_norm_max_blocks() { return GN_BLOCKS; }
+
+static void launch_grad_sqnorm(const float* params, const float* grads, const SegTable& tab, int nb, float grad_scale,
+                               float* gnorm, hipStream_t st) {
+  const int per = std::max(1, (nb + GN_BLOCKS - 1) / GN_BLOCKS);
+  hipLaunchKernelGGL(grad_sqnorm_k, dim3(GN_BLOCKS), dim3(TPB), 0, st, params, grads, tab, grad_scale, per, gnorm);
+}
+
+hipError_t grad_global_norm(const float* params, const float* grads, const OptSeg* segs, int nseg, float grad_scale,
+                            float* gnorm, hipStream_t st) {
+  if (nseg > MAXSEG || nseg < 1 || !gnorm) return hipErrorInvalidValue;
+  SegTable tab;
+  const int nb = build_seg_table(segs, nseg, 0, tab);
+  if (nb < 0) return hipErrorInvalidValue;
+  launch_grad_sqnorm(params, grads, tab, nb, grad_scale, gnorm, st);
+  hipLaunchKernelGGL(gnorm_finish_k, dim3(1), dim3(TPB), 0, st, gnorm);
+  return hipGetLastError();
+}
+
+hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
+                           int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n,
+                           hipStream_t st, const FinArgs* fin, const PermJob* perm, float* slot2, float clip_norm,
+                           float* gnorm) {
+  if (nseg > MAXSEG || nseg < 1) return hipErrorInvalidValue;
+  if (op.rule < OPT_CLASSIC || op.rule > OPT_ADAGRAD) return hipErrorInvalidValue;
+  if (op.rule != OPT_CLASSIC && (!mom || (op.rule != OPT_ADAGRAD && !slot2))) return hipErrorInvalidValue;
+  if (fin && fin->nw > FIN_MAXW) return hipErrorInvalidValue;
+  const bool clip = clip_norm > 0.f;
+  if (clip && (!gnorm || op.guard)) return hipErrorInvalidValue;   // a PS push is never clipped
+  SegTable tab;
+  const int nb = build_seg_table(segs, nseg, l2n, tab);
+  if (nb < 0) return hipErrorInvalidValue;
   (void)total;
   FinArgs fa{};
   int* tickets = nullptr;
@@ -1382,12 +1556,26 @@ hipError_t fused_optimizer(float* params, const float* grads, float* mom, float*
   auto adaptive = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj);
   };
-  switch (op.rule) {
-    case OPT_ADAM: adaptive(adaptive_opt_k<OPT_ADAM>); break;
-    case OPT_RMSPROP: adaptive(adaptive_opt_k<OPT_RMSPROP>); break;
-    case OPT_ADAGRAD: adaptive(adaptive_opt_k<OPT_ADAGRAD>); break;
-    default:
-      hipLaunchKernelGGL(fused_opt_k, grid, dim3(TPB), 0, st, params, grads, mom, ema, bf, tab, step, op, l2, fa, pj);
+  auto clipped = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj,
+                       gnorm, clip_norm);
+  };
+  if (clip) {
+    launch_grad_sqnorm(params, grads, tab, nb, op.grad_scale, gnorm, st);
+    switch (op.rule) {
+      case OPT_ADAM: clipped(clipped_opt_k<OPT_ADAM>); break;
+      case OPT_RMSPROP: clipped(clipped_opt_k<OPT_RMSPROP>); break;
+      case OPT_ADAGRAD: clipped(clipped_opt_k<OPT_ADAGRAD>); break;
+      default: clipped(clipped_opt_k<OPT_CLASSIC>);
+    }
+  } else {
+    switch (op.rule) {
+      case OPT_ADAM: adaptive(adaptive_opt_k<OPT_ADAM>); break;
+      case OPT_RMSPROP: adaptive(adaptive_opt_k<OPT_RMSPROP>); break;
+      case OPT_ADAGRAD: adaptive(adaptive_opt_k<OPT_ADAGRAD>); break;
+      default:
+        hipLaunchKernelGGL(fused_opt_k, grid, dim3(TPB), 0, st, params, grads, mom, ema, bf, tab, step, op, l2, fa, pj);
+    }
   }
   if (fin && !tickets) return finalize_step(*fin, st);
   return hipGetLastError();

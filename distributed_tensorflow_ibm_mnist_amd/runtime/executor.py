@@ -944,4 +944,7 @@ class HipNet:
 
     def read_stats(self) -> Dict[str, float]:
         s = self.stats.detach().cpu().tolist()
-        return {"cross_entropy": s[4], "accuracy": s[5], "total_loss": s[6], "nan": s[2]}
+        out = {"cross_entropy": s[4], "accuracy": s[5], "total_loss": s[6], "nan": s[2]}
+        if self.opt.clip_norm is not None:   # the last update's norm before clipping, and its scale
+            out["global_norm"], out["clip_scale"] = self.fp.gnorm[:2].detach().cpu().tolist()
+        return out

@@ -45,8 +45,15 @@ class OptConfig:
     epsilon: Optional[float] = None   # None: the rule's TF1 default (adam 1e-8, rmsprop 1e-10)
     rmsprop_decay: float = 0.9
     adagrad_initial_accumulator: float = 0.1
+    # tf.clip_by_global_norm of the gradient the rule consumes (grad * grad_scale + wd * p, every
+    # variable, biases included): scaled by clip_norm / max(global_norm, clip_norm).  None: off.
+    clip_norm: Optional[float] = None
 
     def __post_init__(self):
+        if self.clip_norm is not None:
+            self.clip_norm = float(self.clip_norm)
+            if not (math.isfinite(self.clip_norm) and self.clip_norm > 0):
+                raise ValueError(f"clip_norm must be finite and > 0, got {self.clip_norm}")
         if self.rule in ("momentum", "nesterov"):
             self.rule = "sgd"
         if self.rule not in ("sgd",) + ADAPTIVE_RULES:
@@ -65,7 +72,8 @@ class OptConfig:
                          rule=spec.name if adaptive else "sgd", beta1=float(spec.beta1), beta2=float(spec.beta2),
                          epsilon=None if spec.epsilon is None else float(spec.epsilon),
                          rmsprop_decay=float(spec.rmsprop_decay),
-                         adagrad_initial_accumulator=float(spec.adagrad_initial_accumulator))
+                         adagrad_initial_accumulator=float(spec.adagrad_initial_accumulator),
+                         clip_norm=getattr(spec, "clip_norm", None))
 
     def lr_at(self, step: int) -> float:
         if self.decay_steps <= 0:
@@ -128,6 +136,9 @@ class FlatParams:
         # slot2 = Adam v or RMSProp ms, allocated by init_slots() for those rules only
         self.mom = torch.zeros(total, dtype=torch.float32, device=device)
         self.slot2: Optional[torch.Tensor] = None
+        # clipping by global norm: [norm before clipping, scale, the reduction's per-block
+        # partials], allocated by init_slots() when OptConfig.clip_norm is set
+        self.gnorm: Optional[torch.Tensor] = None
         self.ema = torch.zeros(total, dtype=torch.float32, device=device)
         self.bf16 = torch.zeros(max(bf_total, 1), dtype=torch.bfloat16, device=device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
@@ -236,14 +247,21 @@ class FlatParams:
 
     def init_slots(self, cfg: OptConfig) -> None:
         """Give the slots the rule's initial values, allocating the second slot buffer if the
-        rule has one.  The executors call this once at construction (before any graph
-        capture: the captured launch holds the buffer's address)."""
+        rule has one and the global-norm buffer if clipping is on.  The executors call this once
+        at construction (before any graph capture: the captured launch holds the buffers'
+        addresses)."""
         s1, s2 = cfg.slot_init()
         self.mom.fill_(s1)
         if cfg.rule in ("adam", "rmsprop"):
             if self.slot2 is None:
                 self.slot2 = torch.empty(self.total, dtype=torch.float32, device=self.device)
             self.slot2.fill_(s2)
+        if cfg.clip_norm is not None and self.gnorm is None:
+            nblk = 0
+            if self.device.type == "cuda":
+                from ..ops._ext import kernels
+                nblk = int(kernels().grad_norm_max_blocks())
+            self.gnorm = torch.zeros(2 + nblk, dtype=torch.float32, device=self.device)
 
     def ema_view(self, name: str) -> torch.Tensor:
         return self._view(self.ema, name)
@@ -306,10 +324,15 @@ class FlatParams:
         (DeviceLoader.lookahead_job), run by extra blocks of the launch."""
         from ..ops._ext import kernels
         l2 = self.l2 if (track_l2 and self.wd_entries) else None
+        clip = {}
+        if cfg.clip_norm is not None:
+            if self.gnorm is None:
+                raise RuntimeError("clip_norm needs FlatParams.init_slots(cfg) before the first step")
+            clip = {"clip_norm": cfg.clip_norm, "gnorm": self.gnorm}
         if not cfg.adaptive:
             kernels().fused_optimizer(self.params, self.grads, self.mom, self.ema, self.bf16, self.segs, self.step,
                                       cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, cfg.nesterov,
-                                      cfg.use_momentum, grad_scale, cfg.ema_max, l2, fin=fin, perm=perm)
+                                      cfg.use_momentum, grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, **clip)
             return
         if cfg.rule != "adagrad" and self.slot2 is None:
             raise RuntimeError(f"optimizer rule {cfg.rule!r} needs FlatParams.init_slots(cfg) before the first step")
@@ -317,4 +340,4 @@ class FlatParams:
                                   cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, False, False,
                                   grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, rule=cfg.rule, slot2=self.slot2,
                                   beta1=cfg.beta1, beta2=cfg.beta2, epsilon=cfg.epsilon,
-                                  rmsprop_decay=cfg.rmsprop_decay)
+                                  rmsprop_decay=cfg.rmsprop_decay, **clip)

@@ -56,6 +56,17 @@ def torch_update(fp: FlatParams, cfg: OptConfig, grad_scale: float = 1.0) -> Non
                 v = fp.params[e.off:e.off + e.n]
                 fp.l2[e.l2_index] += (v * v).sum()
         g = fp.grads * grad_scale + wd * fp.params
+        if cfg.clip_norm is not None:
+            # tf.clip_by_global_norm in fp32: s = c / max(norm, c) (1 exactly at or below c),
+            # NaN for a non-finite norm
+            if fp.gnorm is None:
+                raise RuntimeError("clip_norm needs FlatParams.init_slots(cfg) before the first step")
+            c = torch.tensor(cfg.clip_norm, dtype=torch.float32, device=g.device)
+            gn = (g * g).sum().sqrt()
+            s = torch.where(torch.isfinite(gn), c / torch.maximum(gn, c), torch.full_like(gn, float("nan")))
+            fp.gnorm[0] = gn
+            fp.gnorm[1] = s
+            g = g * s
         if cfg.adaptive:
             _adaptive_update(fp, cfg, g, lr, step + 1)
         else:
@@ -205,4 +216,7 @@ class TorchNet:
 
     def read_stats(self) -> Dict[str, float]:
         s = self.stats.detach().cpu().tolist()
-        return {"cross_entropy": s[4], "accuracy": s[5], "total_loss": s[6], "nan": s[2]}
+        out = {"cross_entropy": s[4], "accuracy": s[5], "total_loss": s[6], "nan": s[2]}
+        if self.opt.clip_norm is not None:   # the last update's norm before clipping, and its scale
+            out["global_norm"], out["clip_scale"] = self.fp.gnorm[:2].detach().cpu().tolist()
+        return out

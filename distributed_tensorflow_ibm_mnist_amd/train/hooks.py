@@ -191,9 +191,11 @@ class SummarySaverHook(SessionRunHook):
         s = ctx.session
         if s.global_step % self.every == 0:
             st = s.read_stats()
-            self.writer.add_scalars({"loss": st["total_loss"], "cross_entropy": st["cross_entropy"],
-                                     "accuracy": st["accuracy"], "learning_rate": s.learning_rate()},
-                                    s.global_step)
+            scalars = {"loss": st["total_loss"], "cross_entropy": st["cross_entropy"],
+                       "accuracy": st["accuracy"], "learning_rate": s.learning_rate()}
+            if "global_norm" in st:   # clipping by global norm is on: the norm before clipping, the scale
+                scalars["global_norm"], scalars["clip_scale"] = st["global_norm"], st["clip_scale"]
+            self.writer.add_scalars(scalars, s.global_step)
 
 
 class StepCounterHook(SessionRunHook):

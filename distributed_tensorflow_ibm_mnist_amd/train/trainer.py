@@ -76,6 +76,7 @@ def placement_table(replica, cl: Cluster) -> str:
 def train(FLAGS, log=print) -> Dict[str, float]:
     pm.configure_from_flags(FLAGS)
     pm.check_ps_optimizer(FLAGS.job_name, log)    # before setup_distribute opens any socket
+    pm.check_ps_clip_norm(FLAGS.job_name, log)
     max_steps = pm.getMaxSteps()                  # main.py:38-40
     test_interval = pm.getTestInterval()
     batch_size = pm.getTrainBatchSize()

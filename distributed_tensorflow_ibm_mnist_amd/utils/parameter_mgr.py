@@ -46,6 +46,7 @@ DEFAULTS: Dict[str, Any] = {
     "epsilon": None,             # adam 1e-8, rmsprop 1e-10
     "rmsprop_decay": 0.9,
     "adagrad_initial_accumulator": 0.1,
+    "clip_norm": None,           # tf.clip_by_global_norm threshold for every rule; None: off
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -66,6 +67,7 @@ class OptimizerSpec:
     epsilon: Optional[float] = None   # None: the rule's TF1 default
     rmsprop_decay: float = 0.9
     adagrad_initial_accumulator: float = 0.1
+    clip_norm: Optional[float] = None   # clip the gradients by this global norm; None: off
 
 
 _config: Dict[str, Any] = {}
@@ -121,7 +123,7 @@ def configure(source: Union[None, str, Dict[str, Any]] = None, **overrides: Any)
 
 FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", "optimizer", "momentum",
              "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
-             "adagrad_initial_accumulator")
+             "adagrad_initial_accumulator", "clip_norm")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 
 
@@ -138,6 +140,26 @@ def check_ps_optimizer(job_name: str, log=print) -> None:
     if job_name in ("ps", "worker") and name in ADAPTIVE_OPTIMIZERS:
         log(f"optimizer {name!r} is not supported in parameter-server mode (--job_name={job_name}): use "
             f"sgd|momentum|nesterov there; {'|'.join(ADAPTIVE_OPTIMIZERS)} run single-process and data-parallel")
+        raise SystemExit(2)
+
+
+def getClipNorm() -> Optional[float]:
+    """The ``clip_norm`` key: None (off) or a finite threshold > 0."""
+    c = get("clip_norm")
+    if c is None:
+        return None
+    c = float(c)
+    if not (c > 0 and c != float("inf")):
+        raise ValueError(f"clip_norm must be finite and > 0, got {c}")
+    return c
+
+
+def check_ps_clip_norm(job_name: str, log=print) -> None:
+    """The parameter servers apply the update themselves (the native shm loop has its own update
+    code) and none of them clips: a PS or worker task with ``clip_norm`` set exits at start-up."""
+    if job_name in ("ps", "worker") and get("clip_norm") is not None:
+        log(f"clip_norm is not supported in parameter-server mode (--job_name={job_name}): the servers apply "
+            f"the update unclipped; gradient clipping runs single-process and data-parallel")
         raise SystemExit(2)
 
 
@@ -193,7 +215,11 @@ def getValData() -> List[str]:
 
 
 def getOptimizer(lr: Any) -> OptimizerSpec:
-    """Config-driven optimizer choice (``mnist_input.py:261``)."""
+    """Config-driven optimizer choice (``mnist_input.py:261``), with the ``clip_norm`` key."""
+    return dataclasses.replace(_optimizer_rule(lr), clip_norm=getClipNorm())
+
+
+def _optimizer_rule(lr: Any) -> OptimizerSpec:
     name = str(get("optimizer")).lower()
     mom = float(get("momentum"))
     if name in ("sgd", "gradientdescent", "gradient_descent"):

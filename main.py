@@ -46,6 +46,8 @@ flags.DEFINE_float("beta2", -1, "adam: override beta2 (0.999)")
 flags.DEFINE_float("epsilon", -1, "adam / rmsprop: override epsilon (1e-8 / 1e-10)")
 flags.DEFINE_float("rmsprop_decay", -1, "rmsprop: override the decay of the mean square (0.9)")
 flags.DEFINE_float("adagrad_initial_accumulator", -1, "adagrad: override the accumulator's initial value (0.1)")
+flags.DEFINE_float("clip_norm", -1, "clip the gradients by this global norm (tf.clip_by_global_norm) before any "
+                   "rule's update; -1: unset (off unless the config sets it); not in parameter-server mode")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
@@ -88,10 +90,12 @@ flags.DEFINE_float("collective_timeout", 600.0, "process-group timeout (s): a hu
 
 
 def main(argv=None):
-    # a PS / worker task with an adaptive optimizer stops here, before torch is even imported
+    # a PS / worker task with an adaptive optimizer or clip_norm stops here, before torch is even
+    # imported
     from distributed_tensorflow_ibm_mnist_amd.utils import parameter_mgr
     parameter_mgr.configure_from_flags(FLAGS)
     parameter_mgr.check_ps_optimizer(FLAGS.job_name)
+    parameter_mgr.check_ps_clip_norm(FLAGS.job_name)
     if FLAGS.ps_hosts and FLAGS.job_name in ("ps", "worker") and "GPU_MAX_HW_QUEUES" not in os.environ:
         # PS mode only (data-parallel workers keep HIP's default queues, so the RCCL stream
         # does not share a queue with compute): PS tasks are often co-located on one GPU,
