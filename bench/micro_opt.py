@@ -15,7 +15,11 @@ writes params, EMA, the slots and (weights) a bf16 copy:
 reduction launch, 8 B per element read, then the clipped optimizer launch), interleaved with the
 plain launches; C is large by default so the updates themselves stay the same.
 
+--rules also takes lars and lamb (the per-variable norm launch, 8 / 16 B per element read, the ratio
+hand-off chosen by --handoff, then the optimizer launch).
+
     python bench/micro_opt.py [--launches 200] [--rounds 5] [--model reference_cnn] [--clip_norm 1e30]
+                              [--rules momentum,lars,adam,lamb] [--handoff self|launch]
 prints one JSON line.
 """
 import argparse
@@ -27,7 +31,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-BYTES = {"sgd": 22, "momentum": 30, "adam": 38, "rmsprop": 38, "adagrad": 30}
+# lars / lamb: the per-variable norm launch reads params and grads (8 B), lamb's also both slots
+# (16 B), in front of momentum's / adam's traffic
+BYTES = {"sgd": 22, "momentum": 30, "adam": 38, "rmsprop": 38, "adagrad": 30, "lars": 38, "lamb": 54}
+LAYERWISE = ("lars", "lamb")   # never timed with clip_norm (the combination is refused)
 CLIP_BYTES = 8   # the reduction reads params and grads once more
 
 
@@ -40,6 +47,10 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--rules", default="momentum,adam,rmsprop,adagrad")
     ap.add_argument("--clip_norm", type=float, default=None, help="also time each rule with this clip_norm")
+    ap.add_argument("--lars_eta", type=float, default=0.001, help="lars: trust coefficient")
+    ap.add_argument("--handoff", choices=["self", "launch"], default=None,
+                    help="lars / lamb: every apply block sums its variable's partials itself, or a third one-block-"
+                         "per-variable launch does (default: by the model's size)")
     args = ap.parse_args()
 
     import torch
@@ -54,12 +65,17 @@ def main() -> int:
     spec = get_model(args.model, args.in_channels)
     init = init_params(spec, seed=0)
     base_rules = [r for r in args.rules.split(",") if r]
-    rules = base_rules + ([r + "+clip" for r in base_rules] if args.clip_norm else [])
+    rules = base_rules + ([r + "+clip" for r in base_rules if r not in LAYERWISE] if args.clip_norm else [])
+    if args.handoff:
+        from distributed_tensorflow_ibm_mnist_amd.ops._ext import kernels
+        kernels().set_layerwise_self_sum(int(args.handoff == "self"))
     nets = {}
     for key in rules:
         r, clip = key.split("+")[0], (args.clip_norm if key.endswith("+clip") else None)
-        if r in ("adam", "rmsprop", "adagrad"):
+        if r in ("adam", "rmsprop", "adagrad", "lamb"):
             cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r, clip_norm=clip)
+        elif r == "lars":
+            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r, momentum=0.9, lars_eta=args.lars_eta)
         else:
             cfg = OptConfig(lr0=1e-3, ema_max=0.9999, momentum=0.9 if r != "sgd" else 0.0, use_momentum=r != "sgd",
                             clip_norm=clip)
@@ -98,11 +114,19 @@ def main() -> int:
         for r in rules:
             out["rules"][r]["ratio_to_momentum"] = round(out["rules"][r]["us_median"] / base, 3)
             out["rules"][r]["expected_ratio"] = round(out["rules"][r]["bytes_per_element"] / BYTES["momentum"], 3)
+    if any(r in LAYERWISE for r in base_rules):
+        from distributed_tensorflow_ibm_mnist_amd.ops._ext import kernels
+        out["layerwise_handoff"] = {-1: "by size", 0: "launch", 1: "self"}[int(kernels().layerwise_self_sum_mode())]
+        for r, plain in (("lars", "momentum"), ("lamb", "adam")):   # the norm pass's cost next to its byte ratio
+            if r in out["rules"] and plain in out["rules"]:
+                out["rules"][r]["ratio_to_" + plain] = round(out["rules"][r]["us_median"] /
+                                                              out["rules"][plain]["us_median"], 3)
+                out["rules"][r]["expected_ratio_to_" + plain] = round(BYTES[r] / BYTES[plain], 3)
     if args.clip_norm:
         from distributed_tensorflow_ibm_mnist_amd.ops._ext import kernels
         out["clip_norm"] = args.clip_norm
         out["grad_norm_blocks"] = int(kernels().grad_norm_max_blocks())
-        for r in base_rules:   # clipped (two launches) over plain (one), next to the byte ratio
+        for r in (r for r in base_rules if r not in LAYERWISE):   # clipped (two launches) over plain (one)
             c, p = out["rules"][r + "+clip"], out["rules"][r]
             c["ratio_to_unclipped"] = round(c["us_median"] / p["us_median"], 3)
             c["expected_ratio_to_unclipped"] = round(c["bytes_per_element"] / p["bytes_per_element"], 3)

@@ -35,10 +35,11 @@ def parse(argv=None):
     ap.add_argument("--model", default="lenet5", choices=sorted(LABEL))
     ap.add_argument("--in_channels", type=int, default=1)
     ap.add_argument("--batch", type=int, default=128, help="per-rank batch")
-    ap.add_argument("--optimizer", default="momentum", choices=["sgd", "momentum", "nesterov", "adam", "rmsprop", "adagrad"],
+    ap.add_argument("--optimizer", default="momentum", choices=["sgd", "momentum", "nesterov", "adam", "rmsprop", "adagrad", "lars", "lamb"],
                     help="adam / rmsprop / adagrad: TF1 defaults (pass a matching --lr, e.g. 0.001 for adam)")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--clip_norm", type=float, default=None, help="clip the gradients by this global norm")
+    ap.add_argument("--lars_eta", type=float, default=0.001, help="lars: trust coefficient")
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
     ap.add_argument("--probe", type=int, default=10000, help="training images in the accuracy probe")
@@ -79,9 +80,12 @@ def run(args) -> dict:
         if world > 1:
             dist.init_process_group("nccl", device_id=dev)
     spec = get_model(args.model, args.in_channels)
-    if args.optimizer in ("adam", "rmsprop", "adagrad"):
+    if args.optimizer in ("adam", "rmsprop", "adagrad", "lamb"):
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule=args.optimizer,
                         clip_norm=args.clip_norm)
+    elif args.optimizer == "lars":
+        opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule="lars", momentum=0.9,
+                        lars_eta=args.lars_eta)
     else:
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, momentum=0.9 if args.optimizer != "sgd" else 0.0,
                         nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999,

@@ -559,6 +559,7 @@ std::vector<mnistx::OptSeg> read_segs(const Tensor& segs, int64_t total, const T
     s.bft_off = a[i][10];
     s.Jt = (int)a[i][11];
     s.It = (int)a[i][12];
+    s.adapt = a[i][13] != 0 ? 1 : 0;   // lars / lamb: the variable takes its own trust ratio
     TORCH_CHECK(s.off == expect_off, "segments must tile the flat buffer in order");
     TORCH_CHECK(s.n == (int64_t)s.G * s.I * s.J, "segment size mismatch");
     TORCH_CHECK(s.Ip >= s.I && s.Jp >= s.J, "padding");
@@ -581,7 +582,8 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
                      optional<Tensor> guard, int64_t guard_want, optional<Tensor> guard_err, int64_t guard_id,
                      optional<py::tuple> fin, optional<py::tuple> perm, const std::string& rule,
                      optional<Tensor> slot2, double beta1, double beta2, optional<double> epsilon,
-                     double rmsprop_decay, optional<double> clip_norm, optional<Tensor> gnorm) {
+                     double rmsprop_decay, optional<double> clip_norm, optional<Tensor> gnorm, double lars_eta,
+                     optional<Tensor> tnorm) {
   const int64_t total = params.numel();
   check(params, at::kFloat, total, "params");
   check(grads, at::kFloat, total, "grads");
@@ -590,18 +592,25 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
   if (rule == "adam") rule_id = mnistx::OPT_ADAM;
   else if (rule == "rmsprop") rule_id = mnistx::OPT_RMSPROP;
   else if (rule == "adagrad") rule_id = mnistx::OPT_ADAGRAD;
+  else if (rule == "lars") rule_id = mnistx::OPT_LARS;
+  else if (rule == "lamb") rule_id = mnistx::OPT_LAMB;
   else TORCH_CHECK(rule == "sgd" || rule == "momentum" || rule == "nesterov",
-                   "fused_optimizer: unknown rule '", rule, "' (sgd|momentum|nesterov|adam|rmsprop|adagrad)");
+                   "fused_optimizer: unknown rule '", rule, "' (sgd|momentum|nesterov|adam|rmsprop|adagrad|lars|lamb)");
+  const bool layerwise = rule_id == mnistx::OPT_LARS || rule_id == mnistx::OPT_LAMB;
+  if (rule_id == mnistx::OPT_LARS) {   // momentum with a trust ratio: the momentum slot, never Nesterov
+    use_momentum = true;
+    nesterov = false;
+  }
   const bool adaptive = rule_id != mnistx::OPT_CLASSIC;
-  const bool two_slots = rule_id == mnistx::OPT_ADAM || rule_id == mnistx::OPT_RMSPROP;
+  const bool two_slots = rule_id == mnistx::OPT_ADAM || rule_id == mnistx::OPT_RMSPROP || rule_id == mnistx::OPT_LAMB;
   if (use_momentum || adaptive) check(mom, at::kFloat, total, "mom");
   if (two_slots) {
     TORCH_CHECK(slot2.has_value() && slot2->defined(), "fused_optimizer: rule '", rule, "' needs slot2");
     check(*slot2, at::kFloat, total, "slot2");
     TORCH_CHECK(slot2->data_ptr() != mom.data_ptr(), "slot2 aliases mom");
   }
-  if (rule_id == mnistx::OPT_ADAM)
-    TORCH_CHECK(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1, "adam: beta1, beta2 in [0, 1)");
+  if (rule_id == mnistx::OPT_ADAM || rule_id == mnistx::OPT_LAMB)
+    TORCH_CHECK(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1, rule, ": beta1, beta2 in [0, 1)");
   if (rule_id == mnistx::OPT_RMSPROP) TORCH_CHECK(rmsprop_decay >= 0 && rmsprop_decay <= 1, "rmsprop: decay in [0, 1]");
   if (ema_max >= 0) check(ema, at::kFloat, total, "ema");
   check(step, at::kLong, 1, "step");
@@ -626,18 +635,20 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
   op.grad_scale = (float)grad_scale;
   op.ema_max = (float)ema_max;
   op.rule = rule_id;
-  if (rule_id == mnistx::OPT_ADAM) {
+  if (rule_id == mnistx::OPT_ADAM || rule_id == mnistx::OPT_LAMB) {
     op.b1 = (float)beta1;
     op.omb1 = (float)(1.0 - beta1);
     op.b2 = (float)beta2;
     op.omb2 = (float)(1.0 - beta2);
-    op.eps = (float)epsilon.value_or(1e-8);
+    op.eps = (float)epsilon.value_or(rule_id == mnistx::OPT_LAMB ? 1e-6 : 1e-8);
     op.log_b1 = beta1 > 0 ? std::log(beta1) : -1e300;   // beta = 0: b^t = 0, the correction is 1
     op.log_b2 = beta2 > 0 ? std::log(beta2) : -1e300;
   } else if (rule_id == mnistx::OPT_RMSPROP) {
     op.b2 = (float)rmsprop_decay;
     op.omb2 = (float)(1.0 - rmsprop_decay);
     op.eps = (float)epsilon.value_or(1e-10);
+  } else if (rule_id == mnistx::OPT_LARS) {
+    op.eps = (float)epsilon.value_or(0.0);
   }
   if (guard.has_value() && guard->defined()) {   // PS push guard: int64 stamp on the device
     check(*guard, at::kLong, 1, "guard");
@@ -663,6 +674,19 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
     TORCH_CHECK(gnorm->device() == params.device(), "gnorm: on the parameters' device");
     clip = (float)*clip_norm;
     gnp = P<float>(*gnorm);
+  }
+  // layer-wise trust ratios: tnorm = [nvar x (pnorm, unorm, ratio) | the reduction's partials]
+  float* tnp = nullptr;
+  if (layerwise) {
+    TORCH_CHECK(std::isfinite(lars_eta) && lars_eta > 0 && (float)lars_eta > 0.f && std::isfinite((float)lars_eta),
+                "fused_optimizer: lars_eta must be finite and > 0");
+    TORCH_CHECK(!clip_norm.has_value(), "fused_optimizer: rule '", rule, "' cannot be combined with clip_norm");
+    TORCH_CHECK(!(guard.has_value() && guard->defined()), "fused_optimizer: rule '", rule,
+                "' cannot be combined with a push guard (parameter-server mode)");
+    TORCH_CHECK(tnorm.has_value() && tnorm->defined(), "fused_optimizer: rule '", rule, "' needs tnorm");
+    check(*tnorm, at::kFloat, mnistx::var_norm_buffer_size(nseg), "tnorm");
+    TORCH_CHECK(tnorm->device() == params.device(), "tnorm: on the parameters' device");
+    tnp = P<float>(*tnorm);
   }
   // fin: finalize_step's arguments after `step` (the same step tensor), run in this launch
   mnistx::FinArgs fa{};
@@ -703,8 +727,57 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
                                  (use_momentum || adaptive) ? P<float>(mom) : nullptr,
                                  ema_max >= 0 ? P<float>(ema) : nullptr, BFm(bf), sv.data(), nseg, total,
                                  P<const int64_t>(step), op, l2p, l2n, cur_stream(), has_fin ? &fa : nullptr,
-                                 has_perm ? &pj : nullptr, two_slots ? P<float>(*slot2) : nullptr, clip, gnp),
+                                 has_perm ? &pj : nullptr, two_slots ? P<float>(*slot2) : nullptr, clip, gnp,
+                                 (float)lars_eta, tnp),
          "fused_optimizer");
+}
+
+// The per-variable norms and trust ratios alone, as the lars / lamb update computes them:
+// tnorm[3 k .. 3 k + 2] = ||p_k||, ||g_k|| (lars) or ||u_k|| (lamb), r_k afterwards.  Not on the
+// training path.
+void var_norms(Tensor params, Tensor grads, Tensor segs, double grad_scale, Tensor tnorm, const std::string& rule,
+               optional<Tensor> mom, optional<Tensor> slot2, optional<Tensor> step, double beta1, double beta2,
+               optional<double> epsilon, double lars_eta) {
+  const int64_t total = params.numel();
+  check(params, at::kFloat, total, "params");
+  check(grads, at::kFloat, total, "grads");
+  TORCH_CHECK(rule == "lars" || rule == "lamb", "var_norms: rule lars|lamb");
+  const bool lamb = rule == "lamb";
+  TORCH_CHECK(std::isfinite(lars_eta) && (float)lars_eta > 0.f && std::isfinite((float)lars_eta),
+              "var_norms: lars_eta must be finite and > 0");
+  int max_l2 = 0;
+  const std::vector<mnistx::OptSeg> sv = read_segs(segs, total, nullptr, max_l2);
+  check(tnorm, at::kFloat, mnistx::var_norm_buffer_size((int)sv.size()), "tnorm");
+  TORCH_CHECK(grads.device() == params.device() && tnorm.device() == params.device(),
+              "grads / tnorm: on the parameters' device");
+  mnistx::OptParams op{};
+  op.grad_scale = (float)grad_scale;
+  op.rule = lamb ? mnistx::OPT_LAMB : mnistx::OPT_LARS;
+  op.eps = (float)epsilon.value_or(lamb ? 1e-6 : 0.0);
+  const float *mp = nullptr, *sp = nullptr;
+  const int64_t* stp = nullptr;
+  if (lamb) {
+    TORCH_CHECK(mom.has_value() && mom->defined() && slot2.has_value() && slot2->defined() && step.has_value() &&
+                    step->defined(), "var_norms: lamb needs mom, slot2 and step");
+    check(*mom, at::kFloat, total, "mom");
+    check(*slot2, at::kFloat, total, "slot2");
+    check(*step, at::kLong, 1, "step");
+    TORCH_CHECK(mom->device() == params.device() && slot2->device() == params.device() &&
+                    step->device() == params.device(), "mom / slot2 / step: on the parameters' device");
+    TORCH_CHECK(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1, "lamb: beta1, beta2 in [0, 1)");
+    op.b1 = (float)beta1;
+    op.omb1 = (float)(1.0 - beta1);
+    op.b2 = (float)beta2;
+    op.omb2 = (float)(1.0 - beta2);
+    op.log_b1 = beta1 > 0 ? std::log(beta1) : -1e300;
+    op.log_b2 = beta2 > 0 ? std::log(beta2) : -1e300;
+    mp = P<const float>(*mom);
+    sp = P<const float>(*slot2);
+    stp = P<const int64_t>(*step);
+  }
+  hip_ok(mnistx::var_norms(P<const float>(params), P<const float>(grads), mp, sp, sv.data(), (int)sv.size(), stp, op,
+                           (float)lars_eta, P<float>(tnorm), cur_stream()),
+         "var_norms");
 }
 
 // The global norm of g_eff = grad * grad_scale + wd * p alone, as the clipped update computes it:
@@ -1435,7 +1508,17 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("fin") = py::none(), py::arg("perm") = py::none(), py::kw_only(), py::arg("rule") = "sgd",
         py::arg("slot2") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
         py::arg("epsilon") = py::none(), py::arg("rmsprop_decay") = 0.9, py::arg("clip_norm") = py::none(),
-        py::arg("gnorm") = py::none());
+        py::arg("gnorm") = py::none(), py::arg("lars_eta") = 0.001, py::arg("tnorm") = py::none());
+  m.def("var_norms", &var_norms, py::arg("params"), py::arg("grads"), py::arg("segs"), py::arg("grad_scale"),
+        py::arg("tnorm"), py::kw_only(), py::arg("rule") = "lars", py::arg("mom") = py::none(),
+        py::arg("slot2") = py::none(), py::arg("step") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+        py::arg("epsilon") = py::none(), py::arg("lars_eta") = 0.001,
+        "tnorm[3k..3k+2] = ||p_k||, ||g_k|| (lars) or ||u_k|| (lamb), trust ratio r_k; fixed-order sums");
+  m.def("var_norm_buffer_size", [](int64_t nvar) { return (int64_t)mnistx::var_norm_buffer_size((int)nvar); });
+  m.def("set_layerwise_self_sum", [](int64_t mode) { mnistx::set_layerwise_self_sum((int)mode); },
+        "A/B switch of the lars / lamb ratio hand-off: 1 = every apply block sums its variable's partials, "
+        "0 = a one-block-per-variable launch does, -1 (default) = by size (MNISTX_LAYERWISE_SELF_SUM)");
+  m.def("layerwise_self_sum_mode", []() { return (int64_t)mnistx::layerwise_self_sum_mode(); });
   m.def("grad_global_norm", &grad_global_norm, py::arg("params"), py::arg("grads"), py::arg("segs"),
         py::arg("grad_scale"), py::arg("gnorm"),
         "gnorm[0] = sqrt(sum over all segments of (grad * grad_scale + wd * p)^2), fixed-order sums");

@@ -1,7 +1,15 @@
-// The body of fused_opt_k, adaptive_opt_k<RULE> and clipped_opt_k<RULE> (misc.hip), included
-// inside each kernel so that each compiles it as its own code, with the kernel's parameters in scope:
-//   params, grads, mom, slot2, ema, bf, tab, step_p, op, l2, fin, pj, gnorm, clip_norm, and
-//   `constexpr int RULE`, `constexpr bool CLIP`.
+// The body of fused_opt_k, adaptive_opt_k<RULE>, clipped_opt_k<RULE> and layerwise_opt_k<RULE, SELF>
+// (misc.hip), included inside each kernel so that each compiles it as its own code, with the
+// kernel's parameters in scope:
+//   params, grads, mom, slot2, ema, bf, tab, step_p, op, l2, fin, pj, gnorm, clip_norm, tnorm,
+//   lars_eta, lw_per, and `constexpr int RULE`, `constexpr bool CLIP`, `constexpr bool LW_SELF`.
+// RULE = OPT_LARS / OPT_LAMB (layerwise_opt_k only): the variable's trust ratio r_k scales the
+// update.  tnorm holds var_sqnorm_k's per-(variable, block) partials; with LW_SELF every block
+// sums its own variable's partials in the same fixed order (lw_var_sums), so all blocks of a
+// variable hold the bitwise-same r_k and its first block records norms and ratio; without, the
+// block reads the r_k that var_ratio_k wrote.  LARS then runs the classic momentum text on
+// r_k * g_eff (a multiply of its own: r_k = 1 is bit for bit momentum); LAMB recomputes m, v, u
+// through lamb_u, the helper the norm pass measured u with.
 // CLIP (clipped_opt_k only): clip by global norm.  gnorm[2 ..] holds grad_sqnorm_k's per-block
 // partials of sum(g_eff^2); every block sums them itself in the same fixed order (gn_total), so
 // all blocks hold the bitwise-same norm and scale s = clip_norm / max(norm, clip_norm) with no
@@ -12,7 +20,8 @@
 // Everything outside the rule -- the perm job's blocks, the PS guard, EMA, bf16 / W^T copies,
 // l2 partials, the finalize ticket -- is the same text for every rule.
   constexpr bool ADAPT = RULE != OPT_CLASSIC;
-  constexpr bool TWO = RULE == OPT_ADAM || RULE == OPT_RMSPROP;   // rules with a second slot
+  constexpr bool TWO = RULE == OPT_ADAM || RULE == OPT_RMSPROP || RULE == OPT_LAMB;   // rules with a second slot
+  constexpr bool LW = RULE == OPT_LARS || RULE == OPT_LAMB;
   const int use_m = ADAPT ? 1 : op.use_momentum;                   // the first slot is read and written
   __shared__ float red[TPB / 64];
   __shared__ float wsum[FIN_MAXW];
@@ -87,6 +96,32 @@
       gnorm[1] = clip_s;
     }
   }
+  float lw_r = 1.f, lw_ic1 = 1.f, lw_ic2 = 1.f;
+  if constexpr (LW) {   // behind the loads already in flight
+    if constexpr (LW_SELF) {
+      __shared__ float lred[2 * (TPB / 64)];
+      const bool first = (int)blockIdx.x == tab.blk0[si];
+      if (sg.adapt || first) {   // block-uniform
+        float sp, su, pn, un;
+        lw_var_sums(lw_parts(tnorm, tab.n, si), tab.blk0[si], tab.blk0[si + 1], lw_per, lred, sp, su);
+        lw_r = lw_ratio(RULE == OPT_LAMB, sg.adapt, sp, su, lars_eta, op.eps, pn, un);
+        if (first && threadIdx.x == 0) {
+          tnorm[3 * si] = pn;
+          tnorm[3 * si + 1] = un;
+          tnorm[3 * si + 2] = lw_r;
+        }
+      }
+    } else {
+      lw_r = tnorm[3 * si + 2];
+    }
+    if constexpr (RULE == OPT_LAMB) {
+      __shared__ float lcorr[2];
+      if (threadIdx.x == 0) lamb_corr(step, op, lcorr[0], lcorr[1]);
+      __syncthreads();
+      lw_ic1 = lcorr[0];
+      lw_ic2 = lcorr[1];
+    }
+  }
   float lr_t = lr;
   if constexpr (RULE == OPT_ADAM) {
     __shared__ float corr;
@@ -103,7 +138,11 @@
     float p = pv[u];
     if (li0 + u < sg.n) sq += p * p;
     float g;
-    if constexpr (CLIP) {
+    if constexpr (LW) {
+      // g_eff exactly as the norm pass formed it (lw_geff), and as the unclipped kernels contract it
+      g = lw_geff(p, gv[u], op.grad_scale, sg.wd);
+      if constexpr (RULE == OPT_LARS) g = clip_mul(g, lw_r);
+    } else if constexpr (CLIP) {
       // the sum as the unclipped kernels contract it (the gradient's product rounded, the decay's
       // fused), spelled out: left to itself the compiler pairs the two products here and adds
       // them unfused.  Then the scale: s = 1 changes no bit (tests/test_clip_norm_gpu.py).
@@ -129,6 +168,12 @@
       const float acc = mv[u] + g * g;
       mo[u] = acc;
       p -= lr * g * __builtin_amdgcn_rsqf(acc);
+    } else if constexpr (RULE == OPT_LAMB) {
+      float m, v;
+      const float uu = lamb_u(mv[u], sv[u], g, op, lw_ic1, lw_ic2, m, v);
+      mo[u] = m;
+      so[u] = v;
+      p -= lr * clip_mul(uu, lw_r);
     } else {
       float upd = g;
       mo[u] = 0.f;

@@ -332,6 +332,8 @@ struct OptSeg {          // one trainable tensor inside the flat buffers
   int64_t n;             // elements
   int G, I, J;           // master shape [G][I][J]
   int Ip, Jp;            // padded bf16 copy shape [G][Ip][Jp]
+  int adapt;             // OPT_LARS / OPT_LAMB: 1 = scaled by its own trust ratio, 0 = ratio 1 (in
+                         // what was this struct's padding: size and offsets are unchanged)
   int64_t bf_off;        // offset of the bf16 copy (-1: none)
   float wd;              // L2 weight decay (0: none)
   int track_l2;          // accumulate sum(w^2) into l2[seg]
@@ -365,6 +367,12 @@ struct OptParams {
   double log_b1, log_b2;      // Adam: log(beta), for the bias corrections -expm1(t log beta)
 };
 enum { OPT_CLASSIC = 0, OPT_ADAM = 1, OPT_RMSPROP = 2, OPT_ADAGRAD = 3 };   // OPT_CLASSIC: SGD / momentum / Nesterov
+// the layer-wise rules (fused_optimizer's tnorm / lars_eta; g = grad * grad_scale + wd * p, r_k per
+// variable k: 1 unless adapt, both norms > 0; NaN for a non-finite norm):
+//   LARS: r_k = eta ||p_k|| / (||g_k|| + eps);  v = momentum v + r_k g;  p -= lr v       slot: mom = v
+//   LAMB: m, v as Adam;  u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps);
+//         r_k = ||p_k|| / ||u_k||;  p -= lr r_k u                         slots: mom = m, slot2 = v
+enum { OPT_LARS = 4, OPT_LAMB = 5 };
 
 // l2 (optional): [l2n per-tensor sums | fused_optimizer_blocks() per-block partials]
 int fused_optimizer_blocks(const OptSeg* segs, int nseg);
@@ -402,7 +410,26 @@ struct PermJob {
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
                            int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n, hipStream_t st,
                            const FinArgs* fin = nullptr, const PermJob* perm = nullptr, float* slot2 = nullptr,
-                           float clip_norm = 0.f, float* gnorm = nullptr);
+                           float clip_norm = 0.f, float* gnorm = nullptr, float lars_eta = 0.f, float* tnorm = nullptr);
+// OPT_LARS / OPT_LAMB: var_sqnorm_k reduces, per variable, sum(p^2) and sum(g^2) (LARS) or sum(u^2)
+// (LAMB: m, v, u formed in registers from the slots, nothing stored) over the optimizer's own
+// chunk table into per-(variable, block) partials in a fixed order; the norms and the ratio r_k
+// come from those partials either in every block of layerwise_opt_k<RULE>, which sums its own
+// variable's partials (small models: up to 1024 chunks), or in a one-block-per-variable launch
+// (var_ratio_k) in between; then the rule is applied.  No atomics, no ticket in the norm pass, no host sync; the same
+// launches eagerly and under capture.  tnorm (var_norm_buffer_size(nseg) floats):
+// [3 k] ||p_k||  [3 k + 1] ||g_k|| or ||u_k||  [3 k + 2] r_k, then the partials.
+// Invalid together with a PS push guard or clip_norm.
+int var_norm_buffer_size(int nseg);
+// the reduction and the norms / ratios alone (rule = OPT_LARS or OPT_LAMB; op: grad_scale, eps and
+// LAMB's constants; mom, slot2, step: LAMB only)
+hipError_t var_norms(const float* params, const float* grads, const float* mom, const float* slot2,
+                     const OptSeg* segs, int nseg, const int64_t* step, OptParams op, float lars_eta, float* tnorm,
+                     hipStream_t st);
+// A/B switch of the ratio hand-off (MNISTX_LAYERWISE_SELF_SUM): 1 = the apply blocks sum, 0 = the
+// var_ratio_k launch, -1 (default) = by the number of chunks
+void set_layerwise_self_sum(int mode);
+int layerwise_self_sum_mode();
 // Clipping by global norm (clip_norm > 0; tf.clip_by_global_norm): two launches on st, eagerly
 // and under capture alike -- grad_sqnorm_k reduces sum(g_eff^2), g_eff = grad * grad_scale + wd * p
 // over ALL segments, into grad_norm_max_blocks() per-block partials in a fixed order, then the

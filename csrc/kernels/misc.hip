@@ -930,6 +930,68 @@ DEV float clip_mul(float g, float s) {
   return g * s;
 }
 
+// Layer-wise trust ratios (OPT_LARS / OPT_LAMB): the pieces fused_opt_body.h and the norm kernels
+// share.  tnorm: [3 k] ||p_k||  [3 k + 1] ||g_k|| (LARS) or ||u_k|| (LAMB)  [3 k + 2] r_k, then
+// per variable k GN_BLOCKS pairs (sum p^2, sum g^2 or u^2), one per block of var_sqnorm_k.
+DEV float* lw_parts(float* tnorm, int nvar, int k) { return tnorm + 3 * nvar + (size_t)k * (2 * GN_BLOCKS); }
+// g_eff as the unclipped kernels contract it: the gradient's product rounded, the decay's fused
+DEV float lw_geff(float p, float g, float grad_scale, float wd) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(wd, p, g * grad_scale);
+}
+// LAMB's reciprocal bias corrections 1 / (1 - b^t), t = step + 1, as -expm1(t log b) in double
+DEV void lamb_corr(int64_t step, const OptParams& op, float& ic1, float& ic2) {
+  const double t = (double)(step + 1);
+  ic1 = (float)(1.0 / -expm1(t * op.log_b1));
+  ic2 = (float)(1.0 / -expm1(t * op.log_b2));
+}
+// LAMB's new m, v and u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps), contraction pinned:
+// the norm pass and the apply pass get the same bits from the same inputs
+DEV float lamb_u(float m0, float v0, float g, const OptParams& op, float ic1, float ic2, float& m, float& v) {
+#pragma clang fp contract(off)
+  m = op.b1 * m0 + op.omb1 * g;
+  v = op.b2 * v0 + op.omb2 * (g * g);
+  return (m * ic1) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v * ic2) + op.eps);
+}
+// The two sums of one variable over the var_sqnorm_k blocks that walked one of its chunks
+// [c_lo, c_hi) -- every other block stored 0 -- the same bits in every thread of every block
+// that calls it: thread t adds blocks b_lo + t, b_lo + t + TPB, ... in order, then warp_sum, then
+// the waves in index order.  red: 2 * TPB / 64 floats of LDS.  Contains a __syncthreads.
+DEV void lw_var_sums(const float* part, int c_lo, int c_hi, int per, float* red, float& sp, float& su) {
+  float a = 0.f, b = 0.f;
+  if (c_hi > c_lo) {
+    const int b_hi = (c_hi - 1) / per;
+    for (int blk = c_lo / per + (int)threadIdx.x; blk <= b_hi; blk += TPB) {
+      a += part[2 * blk];
+      b += part[2 * blk + 1];
+    }
+  }
+  a = warp_sum(a);
+  b = warp_sum(b);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = a;
+    red[TPB / 64 + (threadIdx.x >> 6)] = b;
+  }
+  __syncthreads();
+  sp = 0.f;
+  su = 0.f;
+#pragma unroll
+  for (int w = 0; w < TPB / 64; ++w) {
+    sp += red[w];
+    su += red[TPB / 64 + w];
+  }
+}
+// r_k from the two sums; pn, un: the norms.  A non-finite norm of an adapted variable gives NaN
+// (the > 0 tests alone would turn a NaN norm into ratio 1 and hide it)
+DEV float lw_ratio(bool lamb, int adapt, float sp, float su, float eta, float eps, float& pn, float& un) {
+  pn = sqrtf(sp);
+  un = sqrtf(su);
+  if (!adapt) return 1.f;
+  if (!isfinite(pn) || !isfinite(un)) return __builtin_nanf("");
+  if (!(pn > 0.f && un > 0.f)) return 1.f;
+  return lamb ? pn / un : eta * pn / (un + eps);
+}
+
 __global__ __launch_bounds__(TPB) void fused_opt_k(float* __restrict__ params, const float* __restrict__ grads,
                                                    float* __restrict__ mom, float* __restrict__ ema,
                                                    bf16_t* __restrict__ bf, SegTable tab,
@@ -940,6 +1002,10 @@ __global__ __launch_bounds__(TPB) void fused_opt_k(float* __restrict__ params, c
   float* const slot2 = nullptr;
   float* const gnorm = nullptr;
   const float clip_norm = 0.f;
+  constexpr bool LW_SELF = false;   // OPT_LARS / OPT_LAMB: layerwise_opt_k only
+  float* const tnorm = nullptr;
+  const float lars_eta = 0.f;
+  const int lw_per = 1;
 #include "fused_opt_body.h"
 }
 
@@ -954,6 +1020,10 @@ __global__ __launch_bounds__(TPB) void adaptive_opt_k(float* __restrict__ params
   constexpr bool CLIP = false;
   float* const gnorm = nullptr;
   const float clip_norm = 0.f;
+  constexpr bool LW_SELF = false;   // OPT_LARS / OPT_LAMB: layerwise_opt_k only
+  float* const tnorm = nullptr;
+  const float lars_eta = 0.f;
+  const int lw_per = 1;
 #include "fused_opt_body.h"
 }
 
@@ -1056,6 +1126,185 @@ __global__ __launch_bounds__(TPB) void clipped_opt_k(float* __restrict__ params,
                                                      float* __restrict__ l2, FinArgs fin, PermJob pj,
                                                      float* __restrict__ gnorm, float clip_norm) {
   constexpr bool CLIP = true;
+  constexpr bool LW_SELF = false;
+  float* const tnorm = nullptr;
+  const float lars_eta = 0.f;
+  const int lw_per = 1;
+#include "fused_opt_body.h"
+}
+
+// Layer-wise trust ratios (OPT_LARS / OPT_LAMB): var_sqnorm_k<LAMB>, then var_ratio_k or none,
+// then layerwise_opt_k<RULE, SELF> on the same stream.  var_sqnorm_k is grad_sqnorm_k per
+// variable: the same chunk decomposition over GN_BLOCKS blocks and the same unrolled / pair /
+// scalar-tail load paths, but two running sums -- p^2 and g_eff^2 (LARS) or u^2 (LAMB, whose new
+// m, v and u are formed in registers from mom and slot2 and never stored) -- that the block
+// flushes to the slot of (variable, block) whenever its chunk range leaves a variable.  A block
+// stores 0 for every variable it holds no chunk of, so nothing stale survives, and no slot is
+// written twice.  Read-only apart from the partials; no atomics, no ticket.
+DEV void lw_flush(float a, float b, float* red, float* dst) {
+  a = warp_sum(a);
+  b = warp_sum(b);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = a;
+    red[TPB / 64 + (threadIdx.x >> 6)] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float ta = 0.f, tb = 0.f;
+    for (int w = 0; w < TPB / 64; ++w) {
+      ta += red[w];
+      tb += red[TPB / 64 + w];
+    }
+    dst[0] = ta;
+    dst[1] = tb;
+  }
+  __syncthreads();   // red is free for the next variable's flush
+}
+
+template <bool LAMB>
+DEV void lw_term(float& ap, float& au, float p, float g, float m0, float v0, float wd, const OptParams& op, float ic1,
+                 float ic2) {
+  float x = lw_geff(p, g, op.grad_scale, wd);
+  if constexpr (LAMB) {
+    float m, v;
+    x = lamb_u(m0, v0, x, op, ic1, ic2, m, v);
+  }
+  ap += p * p;
+  au += x * x;
+}
+
+template <bool LAMB>
+__global__ __launch_bounds__(TPB) void var_sqnorm_k(const float* __restrict__ params, const float* __restrict__ grads,
+                                                    const float* __restrict__ mom, const float* __restrict__ slot2,
+                                                    SegTable tab, const int64_t* __restrict__ step_p, OptParams op,
+                                                    int per, float* __restrict__ tnorm) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  __shared__ float red[2 * (TPB / 64)];
+  float ic1 = 1.f, ic2 = 1.f;
+  if constexpr (LAMB) {
+    __shared__ float lcorr[2];
+    if (threadIdx.x == 0) lamb_corr(*step_p, op, lcorr[0], lcorr[1]);
+    __syncthreads();
+    ic1 = lcorr[0];
+    ic2 = lcorr[1];
+  }
+  const int nc = tab.blk0[tab.n];
+  const int c0 = min(nc, (int)blockIdx.x * per), c1 = min(nc, c0 + per);
+  float ap = 0.f, au = 0.f;
+  int si = 0, c = c0, cur = -1;
+  uint32_t done = 0;   // variables this block has flushed (MAXSEG <= 32)
+  while (c < c1) {
+    while (si + 1 < tab.n && c >= tab.blk0[si + 1]) ++si;
+    if (si != cur) {   // the chunk range crossed into another variable
+      if (cur >= 0) {
+        lw_flush(ap, au, red, lw_parts(tnorm, tab.n, cur) + 2 * blockIdx.x);
+        done |= 1u << cur;
+        ap = au = 0.f;
+      }
+      cur = si;
+    }
+    const int64_t off = tab.s[si].off, n = tab.s[si].n;
+    const float wd = tab.s[si].wd;
+    const int64_t lo = (int64_t)(c - tab.blk0[si]) * OPT_CHUNK;
+    const bool even = (off & 1) == 0;
+    if (even && c + GN_UNROLL <= c1 && lo + GN_UNROLL * OPT_CHUNK <= n) {
+      const int64_t e = off + lo + 2 * (int64_t)threadIdx.x;
+      f32x2_t p2[GN_UNROLL], g2[GN_UNROLL], m2[GN_UNROLL], s2[GN_UNROLL];
+#pragma unroll
+      for (int u = 0; u < GN_UNROLL; ++u) {
+        p2[u] = *(const f32x2_t*)(params + e + u * OPT_CHUNK);
+        g2[u] = *(const f32x2_t*)(grads + e + u * OPT_CHUNK);
+        if constexpr (LAMB) {
+          m2[u] = *(const f32x2_t*)(mom + e + u * OPT_CHUNK);
+          s2[u] = *(const f32x2_t*)(slot2 + e + u * OPT_CHUNK);
+        } else {
+          m2[u] = s2[u] = f32x2_t{0.f, 0.f};
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < GN_UNROLL; ++u) {
+        lw_term<LAMB>(ap, au, p2[u][0], g2[u][0], m2[u][0], s2[u][0], wd, op, ic1, ic2);
+        lw_term<LAMB>(ap, au, p2[u][1], g2[u][1], m2[u][1], s2[u][1], wd, op, ic1, ic2);
+      }
+      c += GN_UNROLL;
+      continue;
+    }
+    // out-of-range elements load element 0 and are never added
+    const int64_t li0 = lo + 2 * (int64_t)threadIdx.x;
+    float pv[OPT_EPT], gv[OPT_EPT], mv[OPT_EPT], sv[OPT_EPT];
+    if (even && li0 + 1 < n) {
+      const f32x2_t p2 = *(const f32x2_t*)(params + off + li0), g2 = *(const f32x2_t*)(grads + off + li0);
+      f32x2_t m2 = {0.f, 0.f}, s2 = {0.f, 0.f};
+      if constexpr (LAMB) {
+        m2 = *(const f32x2_t*)(mom + off + li0);
+        s2 = *(const f32x2_t*)(slot2 + off + li0);
+      }
+#pragma unroll
+      for (int u = 0; u < OPT_EPT; ++u) {
+        pv[u] = p2[u];
+        gv[u] = g2[u];
+        mv[u] = m2[u];
+        sv[u] = s2[u];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < OPT_EPT; ++u) {
+        const int64_t li = li0 + u;
+        const int64_t e = off + (li < n ? li : 0);
+        pv[u] = params[e];
+        gv[u] = grads[e];
+        mv[u] = sv[u] = 0.f;
+        if constexpr (LAMB) {
+          mv[u] = mom[e];
+          sv[u] = slot2[e];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < OPT_EPT; ++u)
+      if (li0 + u < n) lw_term<LAMB>(ap, au, pv[u], gv[u], mv[u], sv[u], wd, op, ic1, ic2);
+    ++c;
+  }
+  if (cur >= 0) {
+    lw_flush(ap, au, red, lw_parts(tnorm, tab.n, cur) + 2 * blockIdx.x);
+    done |= 1u << cur;
+  }
+  if ((int)threadIdx.x < tab.n && !((done >> threadIdx.x) & 1u)) {
+    float* z = lw_parts(tnorm, tab.n, threadIdx.x) + 2 * blockIdx.x;
+    z[0] = 0.f;
+    z[1] = 0.f;
+  }
+}
+
+// norms and ratio of variable blockIdx.x from its partials: the hand-off launch (and var_norms')
+__global__ __launch_bounds__(TPB) void var_ratio_k(SegTable tab, int lamb, float lars_eta, float eps, int per,
+                                                   float* __restrict__ tnorm) {
+  __shared__ float lred[2 * (TPB / 64)];
+  const int k = blockIdx.x;
+  float sp, su, pn, un;
+  lw_var_sums(lw_parts(tnorm, tab.n, k), tab.blk0[k], tab.blk0[k + 1], per, lred, sp, su);
+  const float r = lw_ratio(lamb != 0, tab.s[k].adapt, sp, su, lars_eta, eps, pn, un);
+  if (threadIdx.x == 0) {
+    tnorm[3 * k] = pn;
+    tnorm[3 * k + 1] = un;
+    tnorm[3 * k + 2] = r;
+  }
+}
+
+// the optimizer body compiled for the layer-wise rules (RULE = OPT_LARS, OPT_LAMB); SELF: every
+// block sums its own variable's partials, else it reads the ratio var_ratio_k wrote
+template <int RULE, bool SELF>
+__global__ __launch_bounds__(TPB) void layerwise_opt_k(float* __restrict__ params, const float* __restrict__ grads,
+                                                       float* __restrict__ mom, float* __restrict__ slot2,
+                                                       float* __restrict__ ema, bf16_t* __restrict__ bf, SegTable tab,
+                                                       const int64_t* __restrict__ step_p, OptParams op,
+                                                       float* __restrict__ l2, FinArgs fin, PermJob pj,
+                                                       float* __restrict__ tnorm, float lars_eta, int lw_per) {
+  static_assert(RULE == OPT_LARS || RULE == OPT_LAMB, "layerwise_opt_k: the layer-wise rules only");
+  constexpr bool CLIP = false;
+  constexpr bool LW_SELF = SELF;
+  float* const gnorm = nullptr;
+  const float clip_norm = 0.f;
 #include "fused_opt_body.h"
 }
 
@@ -1524,16 +1773,68 @@ hipError_t grad_global_norm(const float* params, const float* grads, const OptSe
   return hipGetLastError();
 }
 
+int var_norm_buffer_size(int nseg) { return nseg * (3 + 2 * GN_BLOCKS); }
+
+// The ratio hand-off.  Measured (bench/micro_opt.py --handoff): on LeNet-5 (62 K parameters, 125
+// chunks) the apply blocks summing their variable's few partials themselves saves the third
+// launch, 10.8 against 14.0 us (lars); on the reference CNN (3.46 M, 6.8 K chunks) every one of
+// 6.8 K blocks summing up to 450 pairs costs more than the one-block-per-variable launch, 36.5
+// against 34.1 us.  So: self-sum up to LW_SELF_MAX_CHUNKS chunks, the launch above.
+constexpr int LW_SELF_MAX_CHUNKS = 1024;
+static int g_lw_self_sum = -2;   // -2: not read yet; -1: by size; 0 / 1: forced
+void set_layerwise_self_sum(int mode) { g_lw_self_sum = mode < 0 ? -1 : (mode != 0); }
+int layerwise_self_sum_mode() {
+  if (g_lw_self_sum == -2) {
+    const char* e = getenv("MNISTX_LAYERWISE_SELF_SUM");
+    g_lw_self_sum = (e && *e) ? (atoi(e) != 0) : -1;
+  }
+  return g_lw_self_sum;
+}
+
+// var_sqnorm_k over the optimizer's chunk table; returns the chunks per block the readers need
+static int launch_var_sqnorm(const float* params, const float* grads, const float* mom, const float* slot2,
+                             const SegTable& tab, int nb, const int64_t* step, const OptParams& op, float* tnorm,
+                             hipStream_t st) {
+  const int per = std::max(1, (nb + GN_BLOCKS - 1) / GN_BLOCKS);
+  if (op.rule == OPT_LAMB)
+    hipLaunchKernelGGL(var_sqnorm_k<true>, dim3(GN_BLOCKS), dim3(TPB), 0, st, params, grads, mom, slot2, tab, step,
+                       op, per, tnorm);
+  else
+    hipLaunchKernelGGL(var_sqnorm_k<false>, dim3(GN_BLOCKS), dim3(TPB), 0, st, params, grads, mom, slot2, tab, step,
+                       op, per, tnorm);
+  return per;
+}
+
+hipError_t var_norms(const float* params, const float* grads, const float* mom, const float* slot2,
+                     const OptSeg* segs, int nseg, const int64_t* step, OptParams op, float lars_eta, float* tnorm,
+                     hipStream_t st) {
+  if (nseg > MAXSEG || nseg < 1 || !tnorm) return hipErrorInvalidValue;
+  if (op.rule != OPT_LARS && op.rule != OPT_LAMB) return hipErrorInvalidValue;
+  if (op.rule == OPT_LAMB && (!mom || !slot2 || !step)) return hipErrorInvalidValue;
+  SegTable tab;
+  const int nb = build_seg_table(segs, nseg, 0, tab);
+  if (nb < 0) return hipErrorInvalidValue;
+  const int per = launch_var_sqnorm(params, grads, mom, slot2, tab, nb, step, op, tnorm, st);
+  hipLaunchKernelGGL(var_ratio_k, dim3(nseg), dim3(TPB), 0, st, tab, (int)(op.rule == OPT_LAMB), lars_eta, op.eps, per,
+                     tnorm);
+  return hipGetLastError();
+}
+
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
                            int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n,
                            hipStream_t st, const FinArgs* fin, const PermJob* perm, float* slot2, float clip_norm,
-                           float* gnorm) {
+                           float* gnorm, float lars_eta, float* tnorm) {
   if (nseg > MAXSEG || nseg < 1) return hipErrorInvalidValue;
-  if (op.rule < OPT_CLASSIC || op.rule > OPT_ADAGRAD) return hipErrorInvalidValue;
-  if (op.rule != OPT_CLASSIC && (!mom || (op.rule != OPT_ADAGRAD && !slot2))) return hipErrorInvalidValue;
+  if (op.rule < OPT_CLASSIC || op.rule > OPT_LAMB) return hipErrorInvalidValue;
+  const bool lw = op.rule == OPT_LARS || op.rule == OPT_LAMB;
+  if (op.rule != OPT_CLASSIC && (!mom || (op.rule != OPT_ADAGRAD && op.rule != OPT_LARS && !slot2)))
+    return hipErrorInvalidValue;
   if (fin && fin->nw > FIN_MAXW) return hipErrorInvalidValue;
   const bool clip = clip_norm > 0.f;
   if (clip && (!gnorm || op.guard)) return hipErrorInvalidValue;   // a PS push is never clipped
+  // the layer-wise rules: never a PS push, never clipped; LARS runs the classic momentum text
+  if (lw && (!tnorm || op.guard || clip || !(lars_eta > 0.f))) return hipErrorInvalidValue;
+  if (op.rule == OPT_LARS && (!op.use_momentum || op.nesterov)) return hipErrorInvalidValue;
   SegTable tab;
   const int nb = build_seg_table(segs, nseg, l2n, tab);
   if (nb < 0) return hipErrorInvalidValue;
@@ -1560,7 +1861,25 @@ hipError_t fused_optimizer(float* params, const float* grads, float* mom, float*
     hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj,
                        gnorm, clip_norm);
   };
-  if (clip) {
+  if (lw) {
+    const int per = launch_var_sqnorm(params, grads, mom, slot2, tab, nb, step, op, tnorm, st);
+    const int mode = layerwise_self_sum_mode();
+    const bool self = mode < 0 ? nb <= LW_SELF_MAX_CHUNKS : mode != 0;
+    if (!self)
+      hipLaunchKernelGGL(var_ratio_k, dim3(nseg), dim3(TPB), 0, st, tab, (int)(op.rule == OPT_LAMB), lars_eta, op.eps,
+                         per, tnorm);
+    auto layerwise = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj,
+                         tnorm, lars_eta, per);
+    };
+    if (op.rule == OPT_LARS) {
+      if (self) layerwise(layerwise_opt_k<OPT_LARS, true>);
+      else layerwise(layerwise_opt_k<OPT_LARS, false>);
+    } else {
+      if (self) layerwise(layerwise_opt_k<OPT_LAMB, true>);
+      else layerwise(layerwise_opt_k<OPT_LAMB, false>);
+    }
+  } else if (clip) {
     launch_grad_sqnorm(params, grads, tab, nb, op.grad_scale, gnorm, st);
     switch (op.rule) {
       case OPT_ADAM: clipped(clipped_opt_k<OPT_ADAM>); break;

@@ -947,4 +947,6 @@ class HipNet:
         out = {"cross_entropy": s[4], "accuracy": s[5], "total_loss": s[6], "nan": s[2]}
         if self.opt.clip_norm is not None:   # the last update's norm before clipping, and its scale
             out["global_norm"], out["clip_scale"] = self.fp.gnorm[:2].detach().cpu().tolist()
+        if self.opt.layerwise:   # the last update's trust ratio of every adapted variable
+            out.update(self.fp.trust_ratio_stats())
         return out

@@ -25,6 +25,9 @@ import torch
 
 
 ADAPTIVE_RULES = ("adam", "rmsprop", "adagrad")
+# layer-wise trust ratios (LARS on momentum, LAMB on Adam): every variable of rank >= 2 scales its
+# update by a ratio of its own parameter norm to its update norm; biases keep ratio 1
+LAYERWISE_RULES = ("lars", "lamb")
 
 
 @dataclasses.dataclass
@@ -39,15 +42,18 @@ class OptConfig:
     # update rule: "sgd" (SGD / momentum / Nesterov as use_momentum and nesterov say) or one of
     # the adaptive rules "adam" | "rmsprop" | "adagrad" (TF1 semantics and defaults).  With
     # "rmsprop", ``momentum`` is RMSProp's own momentum (TF1 default 0.0).
+    # "lars" (momentum, ``lars_eta``, ``epsilon`` default 0.0) and "lamb" (beta1, beta2,
+    # ``epsilon`` default 1e-6, no decoupled decay) add the layer-wise trust ratio.
     rule: str = "sgd"
     beta1: float = 0.9            # adam
     beta2: float = 0.999          # adam
-    epsilon: Optional[float] = None   # None: the rule's TF1 default (adam 1e-8, rmsprop 1e-10)
+    epsilon: Optional[float] = None   # None: the rule's default (adam 1e-8, rmsprop 1e-10, lars 0, lamb 1e-6)
     rmsprop_decay: float = 0.9
     adagrad_initial_accumulator: float = 0.1
     # tf.clip_by_global_norm of the gradient the rule consumes (grad * grad_scale + wd * p, every
     # variable, biases included): scaled by clip_norm / max(global_norm, clip_norm).  None: off.
     clip_norm: Optional[float] = None
+    lars_eta: float = 0.001       # lars: trust coefficient, r = eta * ||p|| / (||g|| + epsilon)
 
     def __post_init__(self):
         if self.clip_norm is not None:
@@ -56,8 +62,17 @@ class OptConfig:
                 raise ValueError(f"clip_norm must be finite and > 0, got {self.clip_norm}")
         if self.rule in ("momentum", "nesterov"):
             self.rule = "sgd"
-        if self.rule not in ("sgd",) + ADAPTIVE_RULES:
-            raise ValueError(f"unknown update rule {self.rule!r} (sgd|{'|'.join(ADAPTIVE_RULES)})")
+        if self.rule not in ("sgd",) + ADAPTIVE_RULES + LAYERWISE_RULES:
+            raise ValueError(f"unknown update rule {self.rule!r} "
+                             f"(sgd|{'|'.join(ADAPTIVE_RULES + LAYERWISE_RULES)})")
+        if self.rule in LAYERWISE_RULES:
+            if self.clip_norm is not None:
+                raise ValueError(f"rule {self.rule!r} cannot be combined with clip_norm")
+            self.lars_eta = float(self.lars_eta)
+            if not (math.isfinite(self.lars_eta) and self.lars_eta > 0):
+                raise ValueError(f"lars_eta must be finite and > 0, got {self.lars_eta}")
+        if self.rule == "lars":     # momentum with a trust ratio: always the momentum slot
+            self.use_momentum, self.nesterov = True, False
         if self.rule == "adagrad" and not self.adagrad_initial_accumulator > 0:
             raise ValueError("adagrad_initial_accumulator must be > 0")   # as TF1 requires
 
@@ -65,7 +80,7 @@ class OptConfig:
     def from_spec(spec, decay_steps: int, decay_rate: float, ema: float = 0.9999) -> "OptConfig":
         """From a parameter-manager ``OptimizerSpec``."""
         lr = spec.learning_rate
-        adaptive = spec.name in ADAPTIVE_RULES
+        adaptive = spec.name in ADAPTIVE_RULES + LAYERWISE_RULES
         return OptConfig(lr0=float(lr), decay_rate=float(decay_rate), decay_steps=int(decay_steps),
                          momentum=float(spec.momentum), nesterov=bool(spec.nesterov),
                          use_momentum=spec.name == "momentum", ema_max=ema,
@@ -73,7 +88,8 @@ class OptConfig:
                          epsilon=None if spec.epsilon is None else float(spec.epsilon),
                          rmsprop_decay=float(spec.rmsprop_decay),
                          adagrad_initial_accumulator=float(spec.adagrad_initial_accumulator),
-                         clip_norm=getattr(spec, "clip_norm", None))
+                         clip_norm=getattr(spec, "clip_norm", None),
+                         lars_eta=float(getattr(spec, "lars_eta", 0.001)))
 
     def lr_at(self, step: int) -> float:
         if self.decay_steps <= 0:
@@ -85,12 +101,17 @@ class OptConfig:
         return self.rule in ADAPTIVE_RULES
 
     @property
+    def layerwise(self) -> bool:
+        return self.rule in LAYERWISE_RULES
+
+    @property
     def eps(self) -> float:
-        return self.epsilon if self.epsilon is not None else {"adam": 1e-8, "rmsprop": 1e-10}.get(self.rule, 0.0)
+        return self.epsilon if self.epsilon is not None else {"adam": 1e-8, "rmsprop": 1e-10,
+                                                              "lamb": 1e-6}.get(self.rule, 0.0)
 
     def slot_names(self) -> Tuple[Optional[str], Optional[str]]:
         """TF1's slot-variable suffixes of (``FlatParams.mom``, ``FlatParams.slot2``); None: unused."""
-        if self.rule == "adam":
+        if self.rule in ("adam", "lamb"):
             return "Adam", "Adam_1"            # m, v
         if self.rule == "rmsprop":
             return "RMSProp_1", "RMSProp"      # mom, ms (TF1 creates the "rms" slot first)
@@ -139,6 +160,9 @@ class FlatParams:
         # clipping by global norm: [norm before clipping, scale, the reduction's per-block
         # partials], allocated by init_slots() when OptConfig.clip_norm is set
         self.gnorm: Optional[torch.Tensor] = None
+        # lars / lamb: [per variable (parameter norm, gradient / update norm, trust ratio) | the
+        # reduction's per-block partials], allocated by init_slots() for those rules
+        self.tnorm: Optional[torch.Tensor] = None
         self.ema = torch.zeros(total, dtype=torch.float32, device=device)
         self.bf16 = torch.zeros(max(bf_total, 1), dtype=torch.bfloat16, device=device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
@@ -166,7 +190,8 @@ class FlatParams:
         for e in self.entries:
             t = self.bft.get(e.name)
             rows.append([e.off, e.n, e.G, e.I, e.J, e.Ip, e.Jp, e.bf_off, _f32_bits(e.wd or 0.0),
-                         e.l2_index + 1, t[0] if t else -1, t[1] if t else 0, t[2] if t else 0, 0])
+                         e.l2_index + 1, t[0] if t else -1, t[1] if t else 0, t[2] if t else 0,
+                         1 if len(e.shape) >= 2 else 0])   # last: adapted by lars / lamb (the weights)
         self.segs = torch.tensor(rows, dtype=torch.int64)
 
     def enable_transposed(self, tdims: Dict[str, Tuple[int, int]]) -> None:
@@ -247,12 +272,13 @@ class FlatParams:
 
     def init_slots(self, cfg: OptConfig) -> None:
         """Give the slots the rule's initial values, allocating the second slot buffer if the
-        rule has one and the global-norm buffer if clipping is on.  The executors call this once
+        rule has one, the global-norm buffer if clipping is on and the per-variable norm buffer
+        for lars / lamb.  The executors call this once
         at construction (before any graph capture: the captured launch holds the buffers'
         addresses)."""
         s1, s2 = cfg.slot_init()
         self.mom.fill_(s1)
-        if cfg.rule in ("adam", "rmsprop"):
+        if cfg.rule in ("adam", "rmsprop", "lamb"):
             if self.slot2 is None:
                 self.slot2 = torch.empty(self.total, dtype=torch.float32, device=self.device)
             self.slot2.fill_(s2)
@@ -262,6 +288,24 @@ class FlatParams:
                 from ..ops._ext import kernels
                 nblk = int(kernels().grad_norm_max_blocks())
             self.gnorm = torch.zeros(2 + nblk, dtype=torch.float32, device=self.device)
+        if cfg.layerwise and self.tnorm is None:
+            n = 3 * len(self.entries)
+            if self.device.type == "cuda":
+                from ..ops._ext import kernels
+                n = int(kernels().var_norm_buffer_size(len(self.entries)))
+            self.tnorm = torch.zeros(n, dtype=torch.float32, device=self.device)
+
+    def trust_ratios(self) -> Dict[str, Tuple[float, float, float]]:
+        """name -> (parameter norm, gradient (lars) / update (lamb) norm, trust ratio) of the last
+        update, for every variable (the biases' ratio is always 1)."""
+        assert self.tnorm is not None, "trust ratios exist under lars / lamb only"
+        t = self.tnorm[:3 * len(self.entries)].detach().cpu().tolist()
+        return {e.name: (t[3 * i], t[3 * i + 1], t[3 * i + 2]) for i, e in enumerate(self.entries)}
+
+    def trust_ratio_stats(self) -> Dict[str, float]:
+        """``trust_ratio/<var>`` of the adapted variables (rank >= 2), for read_stats()."""
+        tr = self.trust_ratios()
+        return {f"trust_ratio/{e.name}": tr[e.name][2] for e in self.entries if len(e.shape) >= 2}
 
     def ema_view(self, name: str) -> torch.Tensor:
         return self._view(self.ema, name)
@@ -329,6 +373,15 @@ class FlatParams:
             if self.gnorm is None:
                 raise RuntimeError("clip_norm needs FlatParams.init_slots(cfg) before the first step")
             clip = {"clip_norm": cfg.clip_norm, "gnorm": self.gnorm}
+        if cfg.layerwise:
+            if self.tnorm is None or (cfg.rule == "lamb" and self.slot2 is None):
+                raise RuntimeError(f"optimizer rule {cfg.rule!r} needs FlatParams.init_slots(cfg) before the first step")
+            kernels().fused_optimizer(self.params, self.grads, self.mom, self.ema, self.bf16, self.segs, self.step,
+                                      cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, False, cfg.rule == "lars",
+                                      grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, rule=cfg.rule,
+                                      slot2=self.slot2 if cfg.rule == "lamb" else None, beta1=cfg.beta1,
+                                      beta2=cfg.beta2, epsilon=cfg.eps, lars_eta=cfg.lars_eta, tnorm=self.tnorm)
+            return
         if not cfg.adaptive:
             kernels().fused_optimizer(self.params, self.grads, self.mom, self.ema, self.bf16, self.segs, self.step,
                                       cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, cfg.nesterov,

@@ -43,6 +43,45 @@ def _adaptive_update(fp: FlatParams, cfg: OptConfig, g: torch.Tensor, lr: float,
         fp.params.sub_(g / acc.sqrt(), alpha=lr)
 
 
+def _trust_ratio(adapted: bool, pn: torch.Tensor, un: torch.Tensor, num: torch.Tensor) -> torch.Tensor:
+    """``num`` where the variable is adapted and both norms are > 0, else 1; NaN for a non-finite
+    norm of an adapted variable (never hidden behind the > 0 tests)."""
+    one = torch.ones_like(pn)
+    if not adapted:
+        return one
+    r = torch.where((pn > 0) & (un > 0), num, one)
+    return torch.where(torch.isfinite(pn) & torch.isfinite(un), r, torch.full_like(pn, float("nan")))
+
+
+def _layerwise_update(fp: FlatParams, cfg: OptConfig, g: torch.Tensor, lr: float, t: int) -> None:
+    """LARS (momentum) and LAMB (Adam, no decoupled decay) in fp32: one trust ratio per variable
+    of rank >= 2, 1 for the biases; fills ``fp.tnorm[:3 * nvar]`` as the fused kernels do."""
+    if fp.tnorm is None or (cfg.rule == "lamb" and fp.slot2 is None):
+        raise RuntimeError(f"optimizer rule {cfg.rule!r} needs FlatParams.init_slots(cfg) before the first step")
+    if cfg.rule == "lamb":
+        m, v = fp.mom, fp.slot2
+        m.mul_(cfg.beta1).add_(g, alpha=1.0 - cfg.beta1)
+        v.mul_(cfg.beta2).add_(g * g, alpha=1.0 - cfg.beta2)
+        c1 = -math.expm1(t * math.log(cfg.beta1)) if cfg.beta1 > 0 else 1.0
+        c2 = -math.expm1(t * math.log(cfg.beta2)) if cfg.beta2 > 0 else 1.0
+        u = (m / c1) / ((v / c2).sqrt() + cfg.eps)
+    else:
+        u = g
+    scaled = torch.empty_like(u)
+    for i, e in enumerate(fp.entries):
+        sl = slice(e.off, e.off + e.n)
+        pn, un = fp.params[sl].square().sum().sqrt(), u[sl].square().sum().sqrt()
+        num = pn / un if cfg.rule == "lamb" else cfg.lars_eta * pn / (un + cfg.eps)
+        r = _trust_ratio(len(e.shape) >= 2, pn, un, num)
+        fp.tnorm[3 * i], fp.tnorm[3 * i + 1], fp.tnorm[3 * i + 2] = pn, un, r
+        scaled[sl] = u[sl] * r
+    if cfg.rule == "lamb":
+        fp.params.sub_(scaled, alpha=lr)
+    else:
+        fp.mom.mul_(cfg.momentum).add_(scaled)
+        fp.params.sub_(lr * fp.mom)
+
+
 def torch_update(fp: FlatParams, cfg: OptConfig, grad_scale: float = 1.0) -> None:
     """Reference-semantics update (same math as the fused K9 kernel)."""
     with torch.no_grad():
@@ -67,7 +106,9 @@ def torch_update(fp: FlatParams, cfg: OptConfig, grad_scale: float = 1.0) -> Non
             fp.gnorm[0] = gn
             fp.gnorm[1] = s
             g = g * s
-        if cfg.adaptive:
+        if cfg.layerwise:
+            _layerwise_update(fp, cfg, g, lr, step + 1)
+        elif cfg.adaptive:
             _adaptive_update(fp, cfg, g, lr, step + 1)
         else:
             if cfg.use_momentum:
@@ -219,4 +260,6 @@ class TorchNet:
         out = {"cross_entropy": s[4], "accuracy": s[5], "total_loss": s[6], "nan": s[2]}
         if self.opt.clip_norm is not None:   # the last update's norm before clipping, and its scale
             out["global_norm"], out["clip_scale"] = self.fp.gnorm[:2].detach().cpu().tolist()
+        if self.opt.layerwise:   # the last update's trust ratio of every adapted variable
+            out.update(self.fp.trust_ratio_stats())
         return out

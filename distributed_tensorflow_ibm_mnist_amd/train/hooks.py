@@ -195,6 +195,7 @@ class SummarySaverHook(SessionRunHook):
                        "accuracy": st["accuracy"], "learning_rate": s.learning_rate()}
             if "global_norm" in st:   # clipping by global norm is on: the norm before clipping, the scale
                 scalars["global_norm"], scalars["clip_scale"] = st["global_norm"], st["clip_scale"]
+            scalars.update({k: v for k, v in st.items() if k.startswith("trust_ratio/")})   # lars / lamb
             self.writer.add_scalars(scalars, s.global_step)
 
 

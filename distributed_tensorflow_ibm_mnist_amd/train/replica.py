@@ -55,7 +55,7 @@ def state_tensors(net, include_momentum: bool = True) -> Dict[str, np.ndarray]:
         if n2:
             out[f"{e.name}/{n2}"] = slot2[sl].reshape(e.shape).copy()
     step = int(fp.step.item())
-    if include_momentum and net.opt.rule == "adam":
+    if include_momentum and net.opt.rule in ("adam", "lamb"):
         # TF1's Adam keeps beta^t as variables; written as beta^(global_step + 1), ignored on
         # restore (the update derives them from the step)
         out["beta1_power"] = np.asarray(net.opt.beta1 ** (step + 1), dtype=np.float32)

@@ -39,14 +39,15 @@ DEFAULTS: Dict[str, Any] = {
     "batch_size": 128,
     "base_lr": 0.1,
     "lr_decay": 0.1,
-    "optimizer": "sgd",          # sgd | momentum | nesterov | adam | rmsprop | adagrad
+    "optimizer": "sgd",          # sgd | momentum | nesterov | adam | rmsprop | adagrad | lars | lamb
     "momentum": 0.9,             # momentum | nesterov (rmsprop: 0.0 unless the config sets it)
     "beta1": 0.9,                # adam (TF1 defaults)
     "beta2": 0.999,
-    "epsilon": None,             # adam 1e-8, rmsprop 1e-10
+    "epsilon": None,             # adam 1e-8, rmsprop 1e-10, lars 0.0, lamb 1e-6
     "rmsprop_decay": 0.9,
     "adagrad_initial_accumulator": 0.1,
     "clip_norm": None,           # tf.clip_by_global_norm threshold for every rule; None: off
+    "lars_eta": 0.001,           # lars: the trust coefficient
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -58,7 +59,7 @@ ENV_VAR = "MNISTX_PARAMS"
 @dataclasses.dataclass(frozen=True)
 class OptimizerSpec:
     """What ``getOptimizer(lr)`` returns: enough to build the fused K9 update."""
-    name: str            # "sgd" | "momentum" | "adam" | "rmsprop" | "adagrad"
+    name: str            # "sgd" | "momentum" | "adam" | "rmsprop" | "adagrad" | "lars" | "lamb"
     learning_rate: Any   # float, or a callable/step-schedule
     momentum: float = 0.0
     nesterov: bool = False
@@ -68,6 +69,7 @@ class OptimizerSpec:
     rmsprop_decay: float = 0.9
     adagrad_initial_accumulator: float = 0.1
     clip_norm: Optional[float] = None   # clip the gradients by this global norm; None: off
+    lars_eta: float = 0.001             # lars: trust coefficient of the layer-wise ratio
 
 
 _config: Dict[str, Any] = {}
@@ -123,8 +125,9 @@ def configure(source: Union[None, str, Dict[str, Any]] = None, **overrides: Any)
 
 FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", "optimizer", "momentum",
              "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
-             "adagrad_initial_accumulator", "clip_norm")
+             "adagrad_initial_accumulator", "clip_norm", "lars_eta")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
+LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
 
 def configure_from_flags(FLAGS) -> None:
@@ -135,11 +138,13 @@ def configure_from_flags(FLAGS) -> None:
 
 def check_ps_optimizer(job_name: str, log=print) -> None:
     """Parameter-server mode moves exactly one slot buffer between workers and servers, so the
-    adaptive rules are not available there: a PS or worker task exits at start-up."""
+    adaptive rules are not available there, and the servers' update code takes no per-variable
+    norms, so neither are the layer-wise rules: a PS or worker task exits at start-up."""
     name = str(get("optimizer")).lower()
-    if job_name in ("ps", "worker") and name in ADAPTIVE_OPTIMIZERS:
+    if job_name in ("ps", "worker") and name in ADAPTIVE_OPTIMIZERS + LAYERWISE_OPTIMIZERS:
+        others = ADAPTIVE_OPTIMIZERS + (LAYERWISE_OPTIMIZERS if name in LAYERWISE_OPTIMIZERS else ())
         log(f"optimizer {name!r} is not supported in parameter-server mode (--job_name={job_name}): use "
-            f"sgd|momentum|nesterov there; {'|'.join(ADAPTIVE_OPTIMIZERS)} run single-process and data-parallel")
+            f"sgd|momentum|nesterov there; {'|'.join(others)} run single-process and data-parallel")
         raise SystemExit(2)
 
 
@@ -216,7 +221,19 @@ def getValData() -> List[str]:
 
 def getOptimizer(lr: Any) -> OptimizerSpec:
     """Config-driven optimizer choice (``mnist_input.py:261``), with the ``clip_norm`` key."""
-    return dataclasses.replace(_optimizer_rule(lr), clip_norm=getClipNorm())
+    spec, clip = _optimizer_rule(lr), getClipNorm()
+    if clip is not None and spec.name in LAYERWISE_OPTIMIZERS:
+        raise ValueError(f"optimizer {spec.name!r} cannot be combined with clip_norm: the layer-wise trust ratio "
+                         f"already rescales every variable's update")
+    return dataclasses.replace(spec, clip_norm=clip)
+
+
+def getLarsEta() -> float:
+    """The ``lars_eta`` key (LARS trust coefficient): finite and > 0."""
+    eta = float(get("lars_eta"))
+    if not (eta > 0 and eta != float("inf")):
+        raise ValueError(f"lars_eta must be finite and > 0, got {eta}")
+    return eta
 
 
 def _optimizer_rule(lr: Any) -> OptimizerSpec:
@@ -242,7 +259,11 @@ def _optimizer_rule(lr: Any) -> OptimizerSpec:
         if not acc0 > 0:
             raise ValueError(f"adagrad_initial_accumulator must be > 0, got {acc0}")
         return OptimizerSpec("adagrad", lr, adagrad_initial_accumulator=acc0)
-    raise ValueError(f"unsupported optimizer {name!r} (sgd|momentum|nesterov|adam|rmsprop|adagrad)")
+    if name == "lars":     # momentum with a layer-wise trust ratio (epsilon: 0.0 unless set)
+        return OptimizerSpec("lars", lr, mom, False, epsilon=eps, lars_eta=getLarsEta())
+    if name == "lamb":     # Adam with a layer-wise trust ratio (epsilon: 1e-6 unless set)
+        return OptimizerSpec("lamb", lr, beta1=float(get("beta1")), beta2=float(get("beta2")), epsilon=eps)
+    raise ValueError(f"unsupported optimizer {name!r} (sgd|momentum|nesterov|adam|rmsprop|adagrad|lars|lamb)")
 
 
 configure()

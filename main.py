@@ -39,7 +39,8 @@ flags.DEFINE_integer("batch_size", -1, "override getTrainBatchSize() (per replic
 flags.DEFINE_float("base_lr", -1, "override getBaseLearningRate()")
 flags.DEFINE_float("lr_decay", -1, "override getLearningRateDecay()")
 flags.DEFINE_string("optimizer", "", "override getOptimizer(): sgd | momentum | nesterov | adam | rmsprop | adagrad "
-                    "(the adaptive three: TF1 semantics and defaults; not in parameter-server mode)")
+                    "| lars | lamb (the adaptive three: TF1 semantics and defaults; lars / lamb: layer-wise trust "
+                    "ratios on momentum / adam; none of the five in parameter-server mode)")
 flags.DEFINE_float("momentum", -1, "momentum for --optimizer=momentum|nesterov; with rmsprop, its momentum (default 0)")
 flags.DEFINE_float("beta1", -1, "adam: override beta1 (0.9)")
 flags.DEFINE_float("beta2", -1, "adam: override beta2 (0.999)")
@@ -48,6 +49,7 @@ flags.DEFINE_float("rmsprop_decay", -1, "rmsprop: override the decay of the mean
 flags.DEFINE_float("adagrad_initial_accumulator", -1, "adagrad: override the accumulator's initial value (0.1)")
 flags.DEFINE_float("clip_norm", -1, "clip the gradients by this global norm (tf.clip_by_global_norm) before any "
                    "rule's update; -1: unset (off unless the config sets it); not in parameter-server mode")
+flags.DEFINE_float("lars_eta", -1, "lars: override the trust coefficient (0.001)")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
