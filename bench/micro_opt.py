@@ -51,7 +51,18 @@ def main() -> int:
     ap.add_argument("--handoff", choices=["self", "launch"], default=None,
                     help="lars / lamb: every apply block sums its variable's partials itself, or a third one-block-"
                          "per-variable launch does (default: by the model's size)")
+    ap.add_argument("--lr_schedule", default="staircase", choices=["staircase", "polynomial", "cosine"])
+    ap.add_argument("--warmup_steps", type=int, default=0)
+    ap.add_argument("--lr_total_steps", type=int, default=10000, help="polynomial / cosine")
+    ap.add_argument("--lr_end", type=float, default=0.0)
+    ap.add_argument("--lr_power", type=float, default=1.0)
     args = ap.parse_args()
+    # a schedule or a warmup: every rule is timed a second time with it ("<rule>+sched"), at a global
+    # step inside the decay, interleaved with the plain launches
+    sched = {}
+    if args.lr_schedule != "staircase" or args.warmup_steps > 0:
+        sched = dict(schedule=args.lr_schedule, warmup_steps=args.warmup_steps, lr_end=args.lr_end,
+                     lr_power=args.lr_power, total_steps=args.lr_total_steps if args.lr_schedule != "staircase" else 0)
 
     import torch
     if not torch.cuda.is_available():
@@ -66,20 +77,24 @@ def main() -> int:
     init = init_params(spec, seed=0)
     base_rules = [r for r in args.rules.split(",") if r]
     rules = base_rules + ([r + "+clip" for r in base_rules if r not in LAYERWISE] if args.clip_norm else [])
+    rules += [r + "+sched" for r in base_rules] if sched else []
     if args.handoff:
         from distributed_tensorflow_ibm_mnist_amd.ops._ext import kernels
         kernels().set_layerwise_self_sum(int(args.handoff == "self"))
     nets = {}
     for key in rules:
         r, clip = key.split("+")[0], (args.clip_norm if key.endswith("+clip") else None)
+        sk = sched if key.endswith("+sched") else {}
         if r in ("adam", "rmsprop", "adagrad", "lamb"):
-            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r, clip_norm=clip)
+            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r, clip_norm=clip, **sk)
         elif r == "lars":
-            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r, momentum=0.9, lars_eta=args.lars_eta)
+            cfg = OptConfig(lr0=1e-3, ema_max=0.9999, rule=r, momentum=0.9, lars_eta=args.lars_eta, **sk)
         else:
             cfg = OptConfig(lr0=1e-3, ema_max=0.9999, momentum=0.9 if r != "sgd" else 0.0, use_momentum=r != "sgd",
-                            clip_norm=clip)
+                            clip_norm=clip, **sk)
         net = HipNet(spec, 16, dev, init, cfg)      # the executor's own FlatParams layout (pads, W^T copies)
+        if sk:
+            net.fp.step.fill_(cfg.warmup_steps + max(1, (cfg.total_steps - cfg.warmup_steps) // 3))
         net.fp.grads.copy_(torch.randn(net.fp.total, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
                            * 1e-2)
         nets[key] = net
@@ -130,6 +145,11 @@ def main() -> int:
             c, p = out["rules"][r + "+clip"], out["rules"][r]
             c["ratio_to_unclipped"] = round(c["us_median"] / p["us_median"], 3)
             c["expected_ratio_to_unclipped"] = round(c["bytes_per_element"] / p["bytes_per_element"], 3)
+    if sched:
+        out["lr_schedule"] = sched
+        for r in base_rules:   # the scheduled launch (the *_sched_k kernel) over the plain one
+            out["rules"][r + "+sched"]["ratio_to_unscheduled"] = round(out["rules"][r + "+sched"]["us_median"] /
+                                                                       out["rules"][r]["us_median"], 3)
     print(json.dumps(out), flush=True)
     return 0
 

@@ -40,6 +40,12 @@ def parse(argv=None):
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--clip_norm", type=float, default=None, help="clip the gradients by this global norm")
     ap.add_argument("--lars_eta", type=float, default=0.001, help="lars: trust coefficient")
+    ap.add_argument("--lr_schedule", default="staircase", choices=["staircase", "polynomial", "cosine"],
+                    help="polynomial / cosine: decay from the end of the warmup to --lr_end at --lr_total_steps")
+    ap.add_argument("--warmup_steps", type=int, default=0, help="linear warmup in front of any schedule")
+    ap.add_argument("--lr_total_steps", type=int, default=None, help="polynomial / cosine (default: --max_steps)")
+    ap.add_argument("--lr_end", type=float, default=0.0)
+    ap.add_argument("--lr_power", type=float, default=1.0, help="polynomial: the exponent")
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
     ap.add_argument("--probe", type=int, default=10000, help="training images in the accuracy probe")
@@ -80,16 +86,19 @@ def run(args) -> dict:
         if world > 1:
             dist.init_process_group("nccl", device_id=dev)
     spec = get_model(args.model, args.in_channels)
+    total = args.lr_total_steps if args.lr_total_steps is not None else args.max_steps
+    sched = dict(schedule=args.lr_schedule, warmup_steps=args.warmup_steps, lr_end=args.lr_end, lr_power=args.lr_power,
+                 total_steps=total if args.lr_schedule != "staircase" else 0)
     if args.optimizer in ("adam", "rmsprop", "adagrad", "lamb"):
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule=args.optimizer,
-                        clip_norm=args.clip_norm)
+                        clip_norm=args.clip_norm, **sched)
     elif args.optimizer == "lars":
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, ema_max=0.9999, rule="lars", momentum=0.9,
-                        lars_eta=args.lars_eta)
+                        lars_eta=args.lars_eta, **sched)
     else:
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, momentum=0.9 if args.optimizer != "sgd" else 0.0,
                         nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999,
-                        clip_norm=args.clip_norm)
+                        clip_norm=args.clip_norm, **sched)
     init = init_params(spec, seed=args.seed)
     if args.impl == "hip":
         from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet
@@ -165,7 +174,9 @@ def run(args) -> dict:
         "data": f"synthetic 28x28x{args.in_channels} (style {args.style}, noise {args.noise}), random-init weights; "
                 f"probe = first {n_probe} training images",
         "config": {"model": LABEL[args.model], "global_batch": global_batch, "optimizer": args.optimizer,
-                   "lr": args.lr, "eval_every": args.eval_every, "impl": args.impl, "hip_graph": graph is not None,
+                   "lr": args.lr, "lr_schedule": opt.schedule, "warmup_steps": opt.warmup_steps,
+                   "lr_total_steps": opt.total_steps, "lr_end": opt.lr_end, "lr_power": opt.lr_power,
+                   "eval_every": args.eval_every, "impl": args.impl, "hip_graph": graph is not None,
                    "parallelism": f"dp{world}"},
         "history": history[-20:],
     }

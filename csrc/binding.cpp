@@ -1,4 +1,5 @@
 #include <algorithm>
+#include <cctype>
 // Python bindings for the MNIST HIP kernels (torch extension `_kernels`).
 //
 // Every entry point validates device, dtype, contiguity and that each buffer is
@@ -576,6 +577,45 @@ std::vector<mnistx::OptSeg> read_segs(const Tensor& segs, int64_t total, const T
   return sv;
 }
 
+// The learning-rate schedule's keywords (fused_optimizer, lr_at_steps), validated; `who`: the caller's name
+static mnistx::LrSched read_lr_sched(const char* who, const std::string& lr_schedule, int64_t warmup_steps,
+                                     int64_t lr_total_steps, double lr_end, double lr_power) {
+  std::string name = lr_schedule;
+  for (auto& c : name) c = (char)std::tolower((unsigned char)c);
+  mnistx::LrSched sc{};
+  if (name == "staircase") sc.kind = mnistx::LR_STAIRCASE;
+  else if (name == "polynomial") sc.kind = mnistx::LR_POLYNOMIAL;
+  else if (name == "cosine") sc.kind = mnistx::LR_COSINE;
+  else TORCH_CHECK(false, who, ": unknown lr_schedule '", lr_schedule, "' (staircase|polynomial|cosine)");
+  TORCH_CHECK(warmup_steps >= 0, who, ": warmup_steps must be >= 0, got ", warmup_steps);
+  TORCH_CHECK(sc.kind == mnistx::LR_STAIRCASE || lr_total_steps > warmup_steps, who,
+              ": lr_total_steps must be > warmup_steps (", warmup_steps, "), got ", lr_total_steps);
+  TORCH_CHECK(std::isfinite(lr_end) && lr_end >= 0 && std::isfinite((float)lr_end), who,
+              ": lr_end must be finite and >= 0, got ", lr_end);
+  TORCH_CHECK(std::isfinite(lr_power) && lr_power > 0 && (float)lr_power > 0.f && std::isfinite((float)lr_power), who,
+              ": lr_power must be finite and > 0, got ", lr_power);
+  sc.warmup = warmup_steps;
+  sc.total = lr_total_steps;
+  sc.lr_end = (float)lr_end;
+  sc.power = (float)lr_power;
+  return sc;
+}
+
+// out[i] = the learning rate the optimizer launch applies at global step steps[i]: the device's
+// own sched_lr, for tests and for plotting a schedule
+void lr_at_steps(Tensor steps, Tensor out, double lr0, double decay_rate, int64_t decay_steps,
+                 const std::string& lr_schedule, int64_t warmup_steps, int64_t lr_total_steps, double lr_end,
+                 double lr_power) {
+  const int64_t n = steps.numel();
+  check(steps, at::kLong, n, "steps");
+  check(out, at::kFloat, n, "out");
+  TORCH_CHECK(out.device() == steps.device(), "out: on the steps' device");
+  const mnistx::LrSched sc = read_lr_sched("lr_at_steps", lr_schedule, warmup_steps, lr_total_steps, lr_end, lr_power);
+  hip_ok(mnistx::lr_at_steps(P<const int64_t>(steps), P<float>(out), n, (float)lr0, (float)decay_rate, decay_steps, sc,
+                             cur_stream()),
+         "lr_at_steps");
+}
+
 void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor bf, Tensor segs, Tensor step,
                      double lr0, double decay_rate, int64_t decay_steps, double momentum, bool nesterov,
                      bool use_momentum, double grad_scale, double ema_max, optional<Tensor> l2,
@@ -583,10 +623,18 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
                      optional<py::tuple> fin, optional<py::tuple> perm, const std::string& rule,
                      optional<Tensor> slot2, double beta1, double beta2, optional<double> epsilon,
                      double rmsprop_decay, optional<double> clip_norm, optional<Tensor> gnorm, double lars_eta,
-                     optional<Tensor> tnorm) {
+                     optional<Tensor> tnorm, const std::string& lr_schedule, int64_t warmup_steps,
+                     int64_t lr_total_steps, double lr_end, double lr_power) {
   const int64_t total = params.numel();
   check(params, at::kFloat, total, "params");
   check(grads, at::kFloat, total, "grads");
+  // the schedule: the plain staircase (no warmup) is the launch as it always was
+  const mnistx::LrSched sched =
+      read_lr_sched("fused_optimizer", lr_schedule, warmup_steps, lr_total_steps, lr_end, lr_power);
+  const bool scheduled = !mnistx::lr_sched_is_default(sched);
+  TORCH_CHECK(!(scheduled && guard.has_value() && guard->defined()),
+              "fused_optimizer: lr_schedule '", lr_schedule, "' / warmup_steps ", warmup_steps,
+              " cannot be combined with a push guard (parameter-server mode)");
   // rule: the classic names leave the choice to use_momentum / nesterov, as before
   int rule_id = mnistx::OPT_CLASSIC;
   if (rule == "adam") rule_id = mnistx::OPT_ADAM;
@@ -728,7 +776,7 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
                                  ema_max >= 0 ? P<float>(ema) : nullptr, BFm(bf), sv.data(), nseg, total,
                                  P<const int64_t>(step), op, l2p, l2n, cur_stream(), has_fin ? &fa : nullptr,
                                  has_perm ? &pj : nullptr, two_slots ? P<float>(*slot2) : nullptr, clip, gnp,
-                                 (float)lars_eta, tnp),
+                                 (float)lars_eta, tnp, scheduled ? &sched : nullptr),
          "fused_optimizer");
 }
 
@@ -1508,7 +1556,13 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("fin") = py::none(), py::arg("perm") = py::none(), py::kw_only(), py::arg("rule") = "sgd",
         py::arg("slot2") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
         py::arg("epsilon") = py::none(), py::arg("rmsprop_decay") = 0.9, py::arg("clip_norm") = py::none(),
-        py::arg("gnorm") = py::none(), py::arg("lars_eta") = 0.001, py::arg("tnorm") = py::none());
+        py::arg("gnorm") = py::none(), py::arg("lars_eta") = 0.001, py::arg("tnorm") = py::none(),
+        py::arg("lr_schedule") = "staircase", py::arg("warmup_steps") = 0, py::arg("lr_total_steps") = 0,
+        py::arg("lr_end") = 0.0, py::arg("lr_power") = 1.0);
+  m.def("lr_at_steps", &lr_at_steps, py::arg("steps"), py::arg("out"), py::arg("lr0"), py::arg("decay_rate"),
+        py::arg("decay_steps"), py::kw_only(), py::arg("lr_schedule") = "staircase", py::arg("warmup_steps") = 0,
+        py::arg("lr_total_steps") = 0, py::arg("lr_end") = 0.0, py::arg("lr_power") = 1.0,
+        "out[i] = the learning rate the optimizer launch applies at global step steps[i] (the device's own function)");
   m.def("var_norms", &var_norms, py::arg("params"), py::arg("grads"), py::arg("segs"), py::arg("grad_scale"),
         py::arg("tnorm"), py::kw_only(), py::arg("rule") = "lars", py::arg("mom") = py::none(),
         py::arg("slot2") = py::none(), py::arg("step") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,

@@ -2,7 +2,11 @@
 // (misc.hip), included inside each kernel so that each compiles it as its own code, with the
 // kernel's parameters in scope:
 //   params, grads, mom, slot2, ema, bf, tab, step_p, op, l2, fin, pj, gnorm, clip_norm, tnorm,
-//   lars_eta, lw_per, and `constexpr int RULE`, `constexpr bool CLIP`, `constexpr bool LW_SELF`.
+//   lars_eta, lw_per, sc, and `constexpr int RULE`, `constexpr bool CLIP`, `constexpr bool LW_SELF`,
+//   `constexpr bool SCHED`.
+// SCHED (the *_sched_k kernels only): the rate comes from sched_lr -- warmup, polynomial or cosine
+// decay (LrSched sc) -- in place of the staircase line; everything after `lr` is the same text.
+// Without SCHED the staircase line is compiled alone, as before.
 // RULE = OPT_LARS / OPT_LAMB (layerwise_opt_k only): the variable's trust ratio r_k scales the
 // update.  tnorm holds var_sqnorm_k's per-(variable, block) partials; with LW_SELF every block
 // sums its own variable's partials in the same fixed order (lw_var_sums), so all blocks of a
@@ -41,7 +45,11 @@
   const OptSeg sg = tab.s[si];
   const int64_t step = *step_p;
   float lr = op.lr0;
-  if (op.decay_steps > 0) lr *= powf(op.decay_rate, (float)(step / op.decay_steps));  // staircase
+  if constexpr (SCHED) {
+    lr = sched_lr(op.lr0, op.decay_rate, op.decay_steps, sc, step);   // block-uniform
+  } else {
+    if (op.decay_steps > 0) lr *= powf(op.decay_rate, (float)(step / op.decay_steps));  // staircase
+  }
   float ema_d = 0.f;
   if (op.ema_max >= 0.f) ema_d = fminf(op.ema_max, (1.f + (float)step) / (10.f + (float)step));
   const int64_t lo = (int64_t)(blockIdx.x - tab.blk0[si]) * OPT_CHUNK;

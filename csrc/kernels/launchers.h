@@ -374,6 +374,29 @@ enum { OPT_CLASSIC = 0, OPT_ADAM = 1, OPT_RMSPROP = 2, OPT_ADAGRAD = 3 };   // O
 //         r_k = ||p_k|| / ||u_k||;  p -= lr r_k u                         slots: mom = m, slot2 = v
 enum { OPT_LARS = 4, OPT_LAMB = 5 };
 
+// The learning-rate schedule beyond the plain staircase, computed on the device from *step (a
+// captured launch replays its arguments, so a rate computed on the host would freeze).  With
+// t = *step, W = warmup, T = total, all in fp32 (sched_lr, misc.hip):
+//   warm(t) = (t + 1) / W  if W > 0 and t < W, else 1
+//   x(t)    = 0 if t <= W;  1 if t >= T;  else (t - W) / (T - W)
+//   LR_STAIRCASE   base = lr0 * decay_rate ** (t / decay_steps)           (OptParams; T unused)
+//   LR_POLYNOMIAL  base = lr_end + (lr0 - lr_end) * (1 - x) ** power
+//   LR_COSINE      base = lr_end + (lr0 - lr_end) * 0.5 * (1 + cos(pi x))
+//   lr(t) = warm(t) * base(t);  polynomial / cosine: lr_end bitwise for t >= T, lr0 for t = W - 1, W
+// It travels as a kernel argument of its own, after all others, and only to the *_sched_k
+// variants of the optimizer kernels: the launch of a plain staircase (kind LR_STAIRCASE, W = 0)
+// keeps its kernels and its arguments.
+enum { LR_STAIRCASE = 0, LR_POLYNOMIAL = 1, LR_COSINE = 2 };
+struct LrSched {
+  int kind;
+  int64_t warmup, total;
+  float lr_end, power;
+};
+inline bool lr_sched_is_default(const LrSched& s) { return s.kind == LR_STAIRCASE && s.warmup <= 0; }
+// out[i] = the rate the optimizer launch applies at *step == steps[i] (n values on the device)
+hipError_t lr_at_steps(const int64_t* steps, float* out, int64_t n, float lr0, float decay_rate, int64_t decay_steps,
+                       LrSched sched, hipStream_t st);
+
 // l2 (optional): [l2n per-tensor sums | fused_optimizer_blocks() per-block partials]
 int fused_optimizer_blocks(const OptSeg* segs, int nseg);
 // finalize_step's arguments (finalize_k, or the last block of fused_opt_k: ticket != nullptr)
@@ -410,7 +433,8 @@ struct PermJob {
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
                            int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n, hipStream_t st,
                            const FinArgs* fin = nullptr, const PermJob* perm = nullptr, float* slot2 = nullptr,
-                           float clip_norm = 0.f, float* gnorm = nullptr, float lars_eta = 0.f, float* tnorm = nullptr);
+                           float clip_norm = 0.f, float* gnorm = nullptr, float lars_eta = 0.f, float* tnorm = nullptr,
+                           const LrSched* sched = nullptr);   // sched: nullptr = the plain staircase; never with a guard
 // OPT_LARS / OPT_LAMB: var_sqnorm_k reduces, per variable, sum(p^2) and sum(g^2) (LARS) or sum(u^2)
 // (LAMB: m, v, u formed in registers from the slots, nothing stored) over the optimizer's own
 // chunk table into per-(variable, block) partials in a fixed order; the norms and the ratio r_k

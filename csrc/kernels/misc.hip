@@ -992,6 +992,36 @@ DEV float lw_ratio(bool lamb, int adapt, float sp, float su, float eta, float ep
   return lamb ? pn / un : eta * pn / (un + eps);
 }
 
+// The learning rate at global step t (LrSched, launchers.h), in fp32 as written there; every
+// product and sum is an operation of its own.  The staircase is the optimizer body's own line.
+// For polynomial and cosine, t >= T returns lr_end itself and t <= W (x = 0) takes lr0 itself, so
+// neither end depends on how powf or cosf round.  Block-uniform in the optimizer kernels.
+DEV float sched_lr(float lr0, float decay_rate, int64_t decay_steps, const LrSched& sc, int64_t t) {
+#pragma clang fp contract(off)
+  const int64_t W = sc.warmup, T = sc.total;
+  float base = lr0;
+  if (sc.kind == LR_STAIRCASE) {
+    if (decay_steps > 0) base *= powf(decay_rate, (float)(t / decay_steps));
+  } else {
+    if (t >= T) return sc.lr_end;   // T > W: the warmup is over
+    if (t > W) {
+      const float x = (float)(t - W) / (float)(T - W);
+      const float shape = sc.kind == LR_POLYNOMIAL ? powf(1.f - x, sc.power) : 0.5f * (1.f + cosf(3.14159265358979f * x));
+      base = sc.lr_end + (lr0 - sc.lr_end) * shape;
+    }
+  }
+  if (W > 0 && t < W) return (float)(t + 1) / (float)W * base;
+  return base;
+}
+
+// sched_lr for a vector of steps: what lr_at_steps() shows is what the optimizer kernels apply
+__global__ __launch_bounds__(TPB) void lr_at_steps_k(const int64_t* __restrict__ steps, float* __restrict__ out,
+                                                     int64_t n, float lr0, float decay_rate, int64_t decay_steps,
+                                                     LrSched sc) {
+  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB)
+    out[i] = sched_lr(lr0, decay_rate, decay_steps, sc, steps[i]);
+}
+
 __global__ __launch_bounds__(TPB) void fused_opt_k(float* __restrict__ params, const float* __restrict__ grads,
                                                    float* __restrict__ mom, float* __restrict__ ema,
                                                    bf16_t* __restrict__ bf, SegTable tab,
@@ -1006,6 +1036,28 @@ __global__ __launch_bounds__(TPB) void fused_opt_k(float* __restrict__ params, c
   float* const tnorm = nullptr;
   const float lars_eta = 0.f;
   const int lw_per = 1;
+  constexpr bool SCHED = false;     // warmup / polynomial / cosine: the *_sched_k kernels only
+  const LrSched sc{};
+#include "fused_opt_body.h"
+}
+
+// fused_opt_k with the rate from sched_lr (a kernel of its own: fused_opt_k's code and arguments
+// stay what they are)
+__global__ __launch_bounds__(TPB) void fused_opt_sched_k(float* __restrict__ params, const float* __restrict__ grads,
+                                                         float* __restrict__ mom, float* __restrict__ ema,
+                                                         bf16_t* __restrict__ bf, SegTable tab,
+                                                         const int64_t* __restrict__ step_p, OptParams op,
+                                                         float* __restrict__ l2, FinArgs fin, PermJob pj, LrSched sc) {
+  constexpr int RULE = OPT_CLASSIC;
+  constexpr bool CLIP = false;
+  float* const slot2 = nullptr;
+  float* const gnorm = nullptr;
+  const float clip_norm = 0.f;
+  constexpr bool LW_SELF = false;
+  float* const tnorm = nullptr;
+  const float lars_eta = 0.f;
+  const int lw_per = 1;
+  constexpr bool SCHED = true;
 #include "fused_opt_body.h"
 }
 
@@ -1024,6 +1076,26 @@ __global__ __launch_bounds__(TPB) void adaptive_opt_k(float* __restrict__ params
   float* const tnorm = nullptr;
   const float lars_eta = 0.f;
   const int lw_per = 1;
+  constexpr bool SCHED = false;
+  const LrSched sc{};
+#include "fused_opt_body.h"
+}
+
+template <int RULE>
+__global__ __launch_bounds__(TPB) void adaptive_opt_sched_k(float* __restrict__ params, const float* __restrict__ grads,
+                                                            float* __restrict__ mom, float* __restrict__ slot2,
+                                                            float* __restrict__ ema, bf16_t* __restrict__ bf,
+                                                            SegTable tab, const int64_t* __restrict__ step_p,
+                                                            OptParams op, float* __restrict__ l2, FinArgs fin,
+                                                            PermJob pj, LrSched sc) {
+  constexpr bool CLIP = false;
+  float* const gnorm = nullptr;
+  const float clip_norm = 0.f;
+  constexpr bool LW_SELF = false;
+  float* const tnorm = nullptr;
+  const float lars_eta = 0.f;
+  const int lw_per = 1;
+  constexpr bool SCHED = true;
 #include "fused_opt_body.h"
 }
 
@@ -1130,6 +1202,25 @@ __global__ __launch_bounds__(TPB) void clipped_opt_k(float* __restrict__ params,
   float* const tnorm = nullptr;
   const float lars_eta = 0.f;
   const int lw_per = 1;
+  constexpr bool SCHED = false;
+  const LrSched sc{};
+#include "fused_opt_body.h"
+}
+
+template <int RULE>
+__global__ __launch_bounds__(TPB) void clipped_opt_sched_k(float* __restrict__ params, const float* __restrict__ grads,
+                                                           float* __restrict__ mom, float* __restrict__ slot2,
+                                                           float* __restrict__ ema, bf16_t* __restrict__ bf,
+                                                           SegTable tab, const int64_t* __restrict__ step_p,
+                                                           OptParams op, float* __restrict__ l2, FinArgs fin,
+                                                           PermJob pj, float* __restrict__ gnorm, float clip_norm,
+                                                           LrSched sc) {
+  constexpr bool CLIP = true;
+  constexpr bool LW_SELF = false;
+  float* const tnorm = nullptr;
+  const float lars_eta = 0.f;
+  const int lw_per = 1;
+  constexpr bool SCHED = true;
 #include "fused_opt_body.h"
 }
 
@@ -1305,6 +1396,25 @@ __global__ __launch_bounds__(TPB) void layerwise_opt_k(float* __restrict__ param
   constexpr bool LW_SELF = SELF;
   float* const gnorm = nullptr;
   const float clip_norm = 0.f;
+  constexpr bool SCHED = false;
+  const LrSched sc{};
+#include "fused_opt_body.h"
+}
+
+template <int RULE, bool SELF>
+__global__ __launch_bounds__(TPB) void layerwise_opt_sched_k(float* __restrict__ params, const float* __restrict__ grads,
+                                                             float* __restrict__ mom, float* __restrict__ slot2,
+                                                             float* __restrict__ ema, bf16_t* __restrict__ bf,
+                                                             SegTable tab, const int64_t* __restrict__ step_p,
+                                                             OptParams op, float* __restrict__ l2, FinArgs fin,
+                                                             PermJob pj, float* __restrict__ tnorm, float lars_eta,
+                                                             int lw_per, LrSched sc) {
+  static_assert(RULE == OPT_LARS || RULE == OPT_LAMB, "layerwise_opt_sched_k: the layer-wise rules only");
+  constexpr bool CLIP = false;
+  constexpr bool LW_SELF = SELF;
+  float* const gnorm = nullptr;
+  const float clip_norm = 0.f;
+  constexpr bool SCHED = true;
 #include "fused_opt_body.h"
 }
 
@@ -1823,8 +1933,17 @@ hipError_t var_norms(const float* params, const float* grads, const float* mom, 
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
                            int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n,
                            hipStream_t st, const FinArgs* fin, const PermJob* perm, float* slot2, float clip_norm,
-                           float* gnorm, float lars_eta, float* tnorm) {
+                           float* gnorm, float lars_eta, float* tnorm, const LrSched* sched) {
   if (nseg > MAXSEG || nseg < 1) return hipErrorInvalidValue;
+  // the plain staircase keeps its kernels; anything else goes to the *_sched_k variants
+  const bool sch = sched && !lr_sched_is_default(*sched);
+  LrSched sc{};
+  if (sch) {
+    sc = *sched;
+    if (sc.kind < LR_STAIRCASE || sc.kind > LR_COSINE || sc.warmup < 0 || op.guard) return hipErrorInvalidValue;
+    if (sc.kind != LR_STAIRCASE && !(sc.total > sc.warmup)) return hipErrorInvalidValue;
+    if (!(sc.lr_end >= 0.f) || !(sc.power > 0.f)) return hipErrorInvalidValue;
+  }
   if (op.rule < OPT_CLASSIC || op.rule > OPT_LAMB) return hipErrorInvalidValue;
   const bool lw = op.rule == OPT_LARS || op.rule == OPT_LAMB;
   if (op.rule != OPT_CLASSIC && (!mom || (op.rule != OPT_ADAGRAD && op.rule != OPT_LARS && !slot2)))
@@ -1872,7 +1991,19 @@ hipError_t fused_optimizer(float* params, const float* grads, float* mom, float*
       hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj,
                          tnorm, lars_eta, per);
     };
-    if (op.rule == OPT_LARS) {
+    auto layerwise_s = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj,
+                         tnorm, lars_eta, per, sc);
+    };
+    if (sch) {
+      if (op.rule == OPT_LARS) {
+        if (self) layerwise_s(layerwise_opt_sched_k<OPT_LARS, true>);
+        else layerwise_s(layerwise_opt_sched_k<OPT_LARS, false>);
+      } else {
+        if (self) layerwise_s(layerwise_opt_sched_k<OPT_LAMB, true>);
+        else layerwise_s(layerwise_opt_sched_k<OPT_LAMB, false>);
+      }
+    } else if (op.rule == OPT_LARS) {
       if (self) layerwise(layerwise_opt_k<OPT_LARS, true>);
       else layerwise(layerwise_opt_k<OPT_LARS, false>);
     } else {
@@ -1881,11 +2012,36 @@ hipError_t fused_optimizer(float* params, const float* grads, float* mom, float*
     }
   } else if (clip) {
     launch_grad_sqnorm(params, grads, tab, nb, op.grad_scale, gnorm, st);
+    auto clipped_s = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj,
+                         gnorm, clip_norm, sc);
+    };
+    if (sch) {
+      switch (op.rule) {
+        case OPT_ADAM: clipped_s(clipped_opt_sched_k<OPT_ADAM>); break;
+        case OPT_RMSPROP: clipped_s(clipped_opt_sched_k<OPT_RMSPROP>); break;
+        case OPT_ADAGRAD: clipped_s(clipped_opt_sched_k<OPT_ADAGRAD>); break;
+        default: clipped_s(clipped_opt_sched_k<OPT_CLASSIC>);
+      }
+    } else {
+      switch (op.rule) {
+        case OPT_ADAM: clipped(clipped_opt_k<OPT_ADAM>); break;
+        case OPT_RMSPROP: clipped(clipped_opt_k<OPT_RMSPROP>); break;
+        case OPT_ADAGRAD: clipped(clipped_opt_k<OPT_ADAGRAD>); break;
+        default: clipped(clipped_opt_k<OPT_CLASSIC>);
+      }
+    }
+  } else if (sch) {
+    auto adaptive_s = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(TPB), 0, st, params, grads, mom, slot2, ema, bf, tab, step, op, l2, fa, pj, sc);
+    };
     switch (op.rule) {
-      case OPT_ADAM: clipped(clipped_opt_k<OPT_ADAM>); break;
-      case OPT_RMSPROP: clipped(clipped_opt_k<OPT_RMSPROP>); break;
-      case OPT_ADAGRAD: clipped(clipped_opt_k<OPT_ADAGRAD>); break;
-      default: clipped(clipped_opt_k<OPT_CLASSIC>);
+      case OPT_ADAM: adaptive_s(adaptive_opt_sched_k<OPT_ADAM>); break;
+      case OPT_RMSPROP: adaptive_s(adaptive_opt_sched_k<OPT_RMSPROP>); break;
+      case OPT_ADAGRAD: adaptive_s(adaptive_opt_sched_k<OPT_ADAGRAD>); break;
+      default:
+        hipLaunchKernelGGL(fused_opt_sched_k, grid, dim3(TPB), 0, st, params, grads, mom, ema, bf, tab, step, op, l2, fa,
+                           pj, sc);
     }
   } else {
     switch (op.rule) {
@@ -1897,6 +2053,16 @@ hipError_t fused_optimizer(float* params, const float* grads, float* mom, float*
     }
   }
   if (fin && !tickets) return finalize_step(*fin, st);
+  return hipGetLastError();
+}
+
+hipError_t lr_at_steps(const int64_t* steps, float* out, int64_t n, float lr0, float decay_rate, int64_t decay_steps,
+                       LrSched sched, hipStream_t st) {
+  if (n < 0 || sched.kind < LR_STAIRCASE || sched.kind > LR_COSINE || sched.warmup < 0) return hipErrorInvalidValue;
+  if (sched.kind != LR_STAIRCASE && !(sched.total > sched.warmup)) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(lr_at_steps_k, dim3(nblocks(n, TPB, 1024)), dim3(TPB), 0, st, steps, out, n, lr0, decay_rate,
+                     decay_steps, sched);
   return hipGetLastError();
 }
 

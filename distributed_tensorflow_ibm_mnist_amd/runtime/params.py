@@ -8,7 +8,8 @@ creation order (``mnist_input.py:137-205``).  This gives:
   L2 weight decay, SGD / momentum / Nesterov or Adam / RMSProp / Adagrad (TF1
   semantics; a second slot buffer where the rule has one), the staircase LR schedule
   (``mnist_input.py:252-256``, read from the device-side global step — no host
-  sync, hipGraph capturable), the weight EMA with TF's
+  sync, hipGraph capturable) or a linear warmup with polynomial / cosine decay computed
+  the same way, the weight EMA with TF's
   ``min(decay, (1+t)/(10+t))`` (``mnist_input.py:265-267``), and the refresh of
   the zero-padded bf16 weight copies the GEMM kernels read;
 * contiguous gradient buckets for RCCL all-reduce (``parallel/dp.py``);
@@ -28,6 +29,7 @@ ADAPTIVE_RULES = ("adam", "rmsprop", "adagrad")
 # layer-wise trust ratios (LARS on momentum, LAMB on Adam): every variable of rank >= 2 scales its
 # update by a ratio of its own parameter norm to its update norm; biases keep ratio 1
 LAYERWISE_RULES = ("lars", "lamb")
+LR_SCHEDULES = ("staircase", "polynomial", "cosine")
 
 
 @dataclasses.dataclass
@@ -54,8 +56,37 @@ class OptConfig:
     # variable, biases included): scaled by clip_norm / max(global_norm, clip_norm).  None: off.
     clip_norm: Optional[float] = None
     lars_eta: float = 0.001       # lars: trust coefficient, r = eta * ||p|| / (||g|| + epsilon)
+    # the learning-rate schedule, a pure function of global_step t (lr_at; sched_lr in misc.hip):
+    #   lr(t) = warm(t) * base(t),  warm(t) = (t + 1) / warmup_steps for t < warmup_steps, else 1
+    #   "staircase"   base = lr0 * decay_rate ** (t // decay_steps)
+    #   "polynomial"  base = lr_end + (lr0 - lr_end) * (1 - x) ** lr_power
+    #   "cosine"      base = lr_end + (lr0 - lr_end) * 0.5 * (1 + cos(pi x))
+    #   x = 0 up to warmup_steps, then (t - warmup_steps) / (total_steps - warmup_steps), 1 from
+    #   total_steps on (where the rate is lr_end exactly)
+    schedule: str = "staircase"
+    warmup_steps: int = 0
+    total_steps: int = 0          # polynomial | cosine: > warmup_steps
+    lr_end: float = 0.0
+    lr_power: float = 1.0         # polynomial
 
     def __post_init__(self):
+        self.schedule = str(self.schedule).lower()
+        if self.schedule not in LR_SCHEDULES:
+            raise ValueError(f"schedule must be one of {'|'.join(LR_SCHEDULES)}, got {self.schedule!r}")
+        for key in ("warmup_steps", "total_steps"):
+            v = getattr(self, key)
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{key} must be an integer, got {v!r}")
+            setattr(self, key, int(v))
+        if self.warmup_steps < 0:
+            raise ValueError(f"warmup_steps must be >= 0, got {self.warmup_steps}")
+        if self.schedule != "staircase" and self.total_steps <= self.warmup_steps:
+            raise ValueError(f"total_steps must be > warmup_steps ({self.warmup_steps}), got {self.total_steps}")
+        self.lr_end, self.lr_power = float(self.lr_end), float(self.lr_power)
+        if not (math.isfinite(self.lr_end) and self.lr_end >= 0):
+            raise ValueError(f"lr_end must be finite and >= 0, got {self.lr_end}")
+        if not (math.isfinite(self.lr_power) and self.lr_power > 0):
+            raise ValueError(f"lr_power must be finite and > 0, got {self.lr_power}")
         if self.clip_norm is not None:
             self.clip_norm = float(self.clip_norm)
             if not (math.isfinite(self.clip_norm) and self.clip_norm > 0):
@@ -89,12 +120,41 @@ class OptConfig:
                          rmsprop_decay=float(spec.rmsprop_decay),
                          adagrad_initial_accumulator=float(spec.adagrad_initial_accumulator),
                          clip_norm=getattr(spec, "clip_norm", None),
-                         lars_eta=float(getattr(spec, "lars_eta", 0.001)))
+                         lars_eta=float(getattr(spec, "lars_eta", 0.001)),
+                         schedule=getattr(spec, "lr_schedule", "staircase"),
+                         warmup_steps=getattr(spec, "warmup_steps", 0),
+                         total_steps=getattr(spec, "lr_total_steps", 0),
+                         lr_end=getattr(spec, "lr_end", 0.0), lr_power=getattr(spec, "lr_power", 1.0))
+
+    @property
+    def scheduled(self) -> bool:
+        """Anything but the plain staircase: a warmup or one of the decays after it."""
+        return self.schedule != "staircase" or self.warmup_steps > 0
+
+    def schedule_kwargs(self) -> dict:
+        """The fused_optimizer / lr_at_steps keywords of the schedule."""
+        return {"lr_schedule": self.schedule, "warmup_steps": self.warmup_steps, "lr_total_steps": self.total_steps,
+                "lr_end": self.lr_end, "lr_power": self.lr_power}
 
     def lr_at(self, step: int) -> float:
-        if self.decay_steps <= 0:
-            return self.lr0
-        return self.lr0 * self.decay_rate ** (step // self.decay_steps)
+        step = int(step)
+        W, T = self.warmup_steps, self.total_steps
+        if self.schedule == "staircase":
+            base = self.lr0 if self.decay_steps <= 0 else self.lr0 * self.decay_rate ** (step // self.decay_steps)
+        elif step >= T:
+            return self.lr_end                    # exactly, whatever cos(pi) rounds to
+        elif step <= W:
+            base = self.lr0                       # x = 0: the decay starts when the warmup ends
+        else:
+            x = (step - W) / (T - W)
+            if self.schedule == "polynomial":
+                shape = (1.0 - x) ** self.lr_power
+            else:
+                shape = 0.5 * (1.0 + math.cos(math.pi * x))
+            base = self.lr_end + (self.lr0 - self.lr_end) * shape
+        if W > 0 and step < W:
+            return (step + 1) / W * base
+        return base
 
     @property
     def adaptive(self) -> bool:
@@ -368,6 +428,7 @@ class FlatParams:
         (DeviceLoader.lookahead_job), run by extra blocks of the launch."""
         from ..ops._ext import kernels
         l2 = self.l2 if (track_l2 and self.wd_entries) else None
+        sched = cfg.schedule_kwargs()    # the rate itself is computed on the device, from self.step
         clip = {}
         if cfg.clip_norm is not None:
             if self.gnorm is None:
@@ -380,12 +441,14 @@ class FlatParams:
                                       cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, False, cfg.rule == "lars",
                                       grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, rule=cfg.rule,
                                       slot2=self.slot2 if cfg.rule == "lamb" else None, beta1=cfg.beta1,
-                                      beta2=cfg.beta2, epsilon=cfg.eps, lars_eta=cfg.lars_eta, tnorm=self.tnorm)
+                                      beta2=cfg.beta2, epsilon=cfg.eps, lars_eta=cfg.lars_eta, tnorm=self.tnorm,
+                                      **sched)
             return
         if not cfg.adaptive:
             kernels().fused_optimizer(self.params, self.grads, self.mom, self.ema, self.bf16, self.segs, self.step,
                                       cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, cfg.nesterov,
-                                      cfg.use_momentum, grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, **clip)
+                                      cfg.use_momentum, grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, **clip,
+                                      **sched)
             return
         if cfg.rule != "adagrad" and self.slot2 is None:
             raise RuntimeError(f"optimizer rule {cfg.rule!r} needs FlatParams.init_slots(cfg) before the first step")
@@ -393,4 +456,4 @@ class FlatParams:
                                   cfg.lr0, cfg.decay_rate, cfg.decay_steps, cfg.momentum, False, False,
                                   grad_scale, cfg.ema_max, l2, fin=fin, perm=perm, rule=cfg.rule, slot2=self.slot2,
                                   beta1=cfg.beta1, beta2=cfg.beta2, epsilon=cfg.epsilon,
-                                  rmsprop_decay=cfg.rmsprop_decay, **clip)
+                                  rmsprop_decay=cfg.rmsprop_decay, **clip, **sched)

@@ -77,6 +77,7 @@ def train(FLAGS, log=print) -> Dict[str, float]:
     pm.configure_from_flags(FLAGS)
     pm.check_ps_optimizer(FLAGS.job_name, log)    # before setup_distribute opens any socket
     pm.check_ps_clip_norm(FLAGS.job_name, log)
+    pm.check_ps_lr_schedule(FLAGS.job_name, log)
     max_steps = pm.getMaxSteps()                  # main.py:38-40
     test_interval = pm.getTestInterval()
     batch_size = pm.getTrainBatchSize()

@@ -48,6 +48,11 @@ DEFAULTS: Dict[str, Any] = {
     "adagrad_initial_accumulator": 0.1,
     "clip_norm": None,           # tf.clip_by_global_norm threshold for every rule; None: off
     "lars_eta": 0.001,           # lars: the trust coefficient
+    "lr_schedule": "staircase",  # staircase | polynomial | cosine (the last two decay after the warmup)
+    "warmup_steps": 0,           # linear warmup (t + 1) / warmup_steps in front of any schedule; 0: none
+    "lr_total_steps": None,      # polynomial | cosine: the step at which lr_end is reached; None: max_steps
+    "lr_end": 0.0,               # polynomial | cosine: the rate from lr_total_steps on
+    "lr_power": 1.0,             # polynomial: the exponent
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -70,6 +75,12 @@ class OptimizerSpec:
     adagrad_initial_accumulator: float = 0.1
     clip_norm: Optional[float] = None   # clip the gradients by this global norm; None: off
     lars_eta: float = 0.001             # lars: trust coefficient of the layer-wise ratio
+    # the learning-rate schedule (getLrSchedule): kind, warmup and the decay's end
+    lr_schedule: str = "staircase"
+    warmup_steps: int = 0
+    lr_total_steps: int = 0             # polynomial | cosine only
+    lr_end: float = 0.0
+    lr_power: float = 1.0
 
 
 _config: Dict[str, Any] = {}
@@ -125,7 +136,8 @@ def configure(source: Union[None, str, Dict[str, Any]] = None, **overrides: Any)
 
 FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", "optimizer", "momentum",
              "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
-             "adagrad_initial_accumulator", "clip_norm", "lars_eta")
+             "adagrad_initial_accumulator", "clip_norm", "lars_eta", "lr_schedule", "warmup_steps",
+             "lr_total_steps", "lr_end", "lr_power")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
@@ -165,6 +177,75 @@ def check_ps_clip_norm(job_name: str, log=print) -> None:
     if job_name in ("ps", "worker") and get("clip_norm") is not None:
         log(f"clip_norm is not supported in parameter-server mode (--job_name={job_name}): the servers apply "
             f"the update unclipped; gradient clipping runs single-process and data-parallel")
+        raise SystemExit(2)
+
+
+LR_SCHEDULES = ("staircase", "polynomial", "cosine")
+
+
+def _as_int(key: str, v: Any) -> int:
+    """An integer key: 3 and 3.0 pass, 3.5, True and "x" do not."""
+    try:
+        if isinstance(v, bool) or int(v) != float(v):
+            raise ValueError
+        return int(v)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{key} must be an integer, got {v!r}") from None
+
+
+def getLrSchedule() -> str:
+    """The ``lr_schedule`` key: staircase | polynomial | cosine, case-insensitive."""
+    name = str(get("lr_schedule")).lower()
+    if name not in LR_SCHEDULES:
+        raise ValueError(f"lr_schedule must be one of {'|'.join(LR_SCHEDULES)}, got {get('lr_schedule')!r}")
+    return name
+
+
+def getWarmupSteps() -> int:
+    """The ``warmup_steps`` key: an integer >= 0 (0: no warmup)."""
+    w = _as_int("warmup_steps", get("warmup_steps"))
+    if w < 0:
+        raise ValueError(f"warmup_steps must be >= 0, got {w}")
+    return w
+
+
+def getLrTotalSteps() -> int:
+    """The ``lr_total_steps`` key (default ``max_steps``): an integer > ``warmup_steps``.  Only
+    polynomial and cosine read it."""
+    t = get("lr_total_steps")
+    t = getMaxSteps() if t is None else _as_int("lr_total_steps", t)
+    w = getWarmupSteps()
+    if t <= w:
+        raise ValueError(f"lr_total_steps must be > warmup_steps ({w}), got {t}")
+    return t
+
+
+def getLrEnd() -> float:
+    """The ``lr_end`` key: finite and >= 0."""
+    e = float(get("lr_end"))
+    if not (e >= 0 and e != float("inf")):
+        raise ValueError(f"lr_end must be finite and >= 0, got {e}")
+    return e
+
+
+def getLrPower() -> float:
+    """The ``lr_power`` key (polynomial): finite and > 0."""
+    p = float(get("lr_power"))
+    if not (p > 0 and p != float("inf")):
+        raise ValueError(f"lr_power must be finite and > 0, got {p}")
+    return p
+
+
+def check_ps_lr_schedule(job_name: str, log=print) -> None:
+    """The parameter servers' update code knows the staircase alone: a PS or worker task with another
+    ``lr_schedule`` or a warmup exits at start-up."""
+    if job_name not in ("ps", "worker"):
+        return
+    name, w = getLrSchedule(), getWarmupSteps()
+    if name != "staircase" or w > 0:
+        what = f"lr_schedule {name!r}" if name != "staircase" else f"warmup_steps {w}"
+        log(f"{what} is not supported in parameter-server mode (--job_name={job_name}): the servers apply the "
+            f"staircase rate; warmup and the polynomial / cosine schedules run single-process and data-parallel")
         raise SystemExit(2)
 
 
@@ -225,7 +306,12 @@ def getOptimizer(lr: Any) -> OptimizerSpec:
     if clip is not None and spec.name in LAYERWISE_OPTIMIZERS:
         raise ValueError(f"optimizer {spec.name!r} cannot be combined with clip_norm: the layer-wise trust ratio "
                          f"already rescales every variable's update")
-    return dataclasses.replace(spec, clip_norm=clip)
+    kind = getLrSchedule()
+    # lr_total_steps and lr_power are only read by the schedules that use them
+    total = getLrTotalSteps() if kind != "staircase" else 0
+    power = getLrPower() if kind == "polynomial" else 1.0
+    return dataclasses.replace(spec, clip_norm=clip, lr_schedule=kind, warmup_steps=getWarmupSteps(),
+                               lr_total_steps=total, lr_end=getLrEnd(), lr_power=power)
 
 
 def getLarsEta() -> float:

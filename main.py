@@ -50,6 +50,13 @@ flags.DEFINE_float("adagrad_initial_accumulator", -1, "adagrad: override the acc
 flags.DEFINE_float("clip_norm", -1, "clip the gradients by this global norm (tf.clip_by_global_norm) before any "
                    "rule's update; -1: unset (off unless the config sets it); not in parameter-server mode")
 flags.DEFINE_float("lars_eta", -1, "lars: override the trust coefficient (0.001)")
+flags.DEFINE_string("lr_schedule", "", "learning-rate schedule: staircase (default) | polynomial | cosine; the last two "
+                    "decay from the end of the warmup to --lr_end at --lr_total_steps; not in parameter-server mode")
+flags.DEFINE_integer("warmup_steps", -1, "linear warmup (step + 1) / warmup_steps in front of any schedule (0: none); "
+                     "not in parameter-server mode")
+flags.DEFINE_integer("lr_total_steps", -1, "polynomial | cosine: the step at which --lr_end is reached (max_steps)")
+flags.DEFINE_float("lr_end", -1, "polynomial | cosine: the rate from --lr_total_steps on (0.0)")
+flags.DEFINE_float("lr_power", -1, "polynomial: the exponent (1.0)")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
@@ -92,12 +99,13 @@ flags.DEFINE_float("collective_timeout", 600.0, "process-group timeout (s): a hu
 
 
 def main(argv=None):
-    # a PS / worker task with an adaptive optimizer or clip_norm stops here, before torch is even
-    # imported
+    # a PS / worker task with an adaptive optimizer, clip_norm, a warmup or a schedule other than the
+    # staircase stops here, before torch is even imported
     from distributed_tensorflow_ibm_mnist_amd.utils import parameter_mgr
     parameter_mgr.configure_from_flags(FLAGS)
     parameter_mgr.check_ps_optimizer(FLAGS.job_name)
     parameter_mgr.check_ps_clip_norm(FLAGS.job_name)
+    parameter_mgr.check_ps_lr_schedule(FLAGS.job_name)
     if FLAGS.ps_hosts and FLAGS.job_name in ("ps", "worker") and "GPU_MAX_HW_QUEUES" not in os.environ:
         # PS mode only (data-parallel workers keep HIP's default queues, so the RCCL stream
         # does not share a queue with compute): PS tasks are often co-located on one GPU,
