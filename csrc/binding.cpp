@@ -1,5 +1,6 @@
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 // Python bindings for the MNIST HIP kernels (torch extension `_kernels`).
 //
 // Every entry point validates device, dtype, contiguity and that each buffer is
@@ -341,9 +342,17 @@ void lrn_pool_bwd(Tensor x, Tensor dP, Tensor arg, Tensor dx, int64_t Nb, int64_
          "lrn_pool_bwd");
 }
 
+// label_smoothing of the softmax-CE bindings: finite, 0 <= eps < 1
+float smoothing_arg(double eps, const char* op) {
+  TORCH_CHECK_VALUE(std::isfinite(eps) && eps >= 0.0 && eps < 1.0, op, ": label_smoothing must be finite with 0 <= "
+              "label_smoothing < 1, got ", eps);
+  return (float)eps;
+}
+
 int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t B, int64_t NC, double scale,
                    optional<Tensor> dlogits, int64_t ldd, optional<Tensor> stats, optional<Tensor> probs,
-                   optional<Tensor> work, bool defer_stats, optional<Tensor> dbias) {
+                   optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing) {
+  const float eps = smoothing_arg(label_smoothing, "softmax_ce");
   TORCH_CHECK(ldl >= NC, "ldl < NC");
   check(logits, at::kFloat, B * ldl, "logits");   // whole padded rows (vector loads)
   const int32_t* lab = nullptr;
@@ -351,6 +360,7 @@ int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t 
     check(*labels, at::kInt, B, "labels");
     lab = P<const int32_t>(*labels);
   }
+  TORCH_CHECK(eps == 0.f || lab != nullptr, "softmax_ce: label_smoothing needs labels");
   mnistx::bf16_t* dl = nullptr;
   if (dlogits.has_value() && dlogits->defined()) {
     TORCH_CHECK(lab != nullptr, "dlogits needs labels");
@@ -384,7 +394,7 @@ int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t 
   }
   int deferred = 0;
   hip_ok(mnistx::softmax_ce(P<const float>(logits), (int)ldl, lab, (int)B, (int)NC, (float)scale, dl, (int)ldd, st, pr,
-                            wk, cur_stream(), defer_stats ? &deferred : nullptr, db),
+                            wk, cur_stream(), defer_stats ? &deferred : nullptr, db, eps),
          "softmax_ce");
   return deferred;   // blocks whose CE partials the caller's finalize_step must combine
 }
@@ -402,7 +412,8 @@ bool ce_tail_supported(int64_t d0, int64_t nc, int64_t B) { return mnistx::ce_ta
 // the reference CNN's softmax_linear + softmax CE (+ data gradient masked by x > 0): mlp_head.hip ce_tail_k
 void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t nb, double scale, Tensor logits,
              optional<Tensor> dl, optional<Tensor> dx, Tensor stats, optional<Tensor> work, bool defer_stats,
-             optional<Tensor> dbias) {
+             optional<Tensor> dbias, double label_smoothing) {
+  const float eps = smoothing_arg(label_smoothing, "ce_tail");
   TORCH_CHECK(mnistx::ce_tail_supported(192, (int)nc, (int)std::max<int64_t>(nb, 1)), "ce_tail: unsupported geometry");
   check(x, at::kBFloat16, nb * 192, "x");
   check(w5t, at::kBFloat16, 16 * 192, "w5t");
@@ -430,16 +441,18 @@ void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t
     check(*dbias, at::kFloat, (int64_t)mnistx::ce_tail_blocks((int)nb) * 16, "dbias");
     db = P<float>(*dbias);
   }
+  TORCH_CHECK(eps == 0.f || pdl != nullptr, "ce_tail: label_smoothing is a training quantity and needs dl");
   hip_ok(mnistx::ce_tail(BF(x), BF(w5t), P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale,
                          P<float>(logits), pdl, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr, cur_stream(),
-                         defer_stats ? 1 : 0, db),
+                         defer_stats ? 1 : 0, db, eps),
          "ce_tail");
 }
 
 void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4, int64_t n2, Tensor w5t, Tensor b5,
               int64_t nc, Tensor labels, int64_t nb, double scale, Tensor h3, Tensor h4, Tensor logits,
               optional<Tensor> dl, optional<Tensor> dh4, optional<Tensor> dh3, optional<Tensor> dx, Tensor stats,
-              optional<Tensor> work, bool defer_stats, optional<Tensor> dbias) {
+              optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing) {
+  const float eps = smoothing_arg(label_smoothing, "mlp_head");
   TORCH_CHECK(mnistx::mlp_head_supported(400, 120, 88, 16, (int)n1, (int)n2, (int)nc, (int)std::max<int64_t>(nb, 1)),
               "mlp_head: unsupported geometry");
   check(x, at::kBFloat16, nb * 400, "x");
@@ -478,10 +491,11 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
     check(*dbias, at::kFloat, (int64_t)mnistx::mlp_head_blocks((int)nb) * 16, "dbias");
     db = P<float>(*dbias);
   }
+  TORCH_CHECK(eps == 0.f || pdl != nullptr, "mlp_head: label_smoothing is a training quantity and needs dl");
   hip_ok(mnistx::mlp_head(BF(x), BF(w3t), P<const float>(b3), (int)n1, BF(w4t), P<const float>(b4), (int)n2, BF(w5t),
                           P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale, BFm(h3),
                           BFm(h4), P<float>(logits), pdl, pdh4, pdh3, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr,
-                          cur_stream(), (defer_stats && has_work) ? 1 : 0, db),
+                          cur_stream(), (defer_stats && has_work) ? 1 : 0, db, eps),
          "mlp_head");
 }
 
@@ -1385,7 +1399,8 @@ void f32_lrn_pool_bwd(Tensor x, Tensor dy, Tensor arg, Tensor dx, int64_t Nb, in
 
 void f32_softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t B, int64_t NC, double scale,
                     optional<Tensor> dlogits, int64_t ldd, optional<Tensor> stats, optional<Tensor> probs,
-                    optional<Tensor> work) {
+                    optional<Tensor> work, double label_smoothing) {
+  const float eps = smoothing_arg(label_smoothing, "f32_softmax_ce");
   TORCH_CHECK(ldl >= NC, "ldl < NC");
   check(logits, at::kFloat, span(B, ldl, NC), "logits");
   const int32_t* lab = nullptr;
@@ -1414,8 +1429,9 @@ void f32_softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t
     check(*work, at::kFloat, 4 * 1024 + 1, "work");
     wk = P<float>(*work);
   }
+  TORCH_CHECK(eps == 0.f || lab != nullptr, "f32_softmax_ce: label_smoothing needs labels");
   hip_ok(mnistx::f32_softmax_ce(P<const float>(logits), (int)ldl, lab, (int)B, (int)NC, (float)scale, dl, (int)ldd,
-                                st, pr, wk, cur_stream()),
+                                st, pr, wk, cur_stream(), eps),
          "f32_softmax_ce");
 }
 
@@ -1461,7 +1477,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("f32_lrn_pool_bwd", &f32_lrn_pool_bwd);
   m.def("f32_softmax_ce", &f32_softmax_ce, py::arg("logits"), py::arg("ldl"), py::arg("labels"), py::arg("B"),
         py::arg("NC"), py::arg("scale"), py::arg("dlogits"), py::arg("ldd"), py::arg("stats"), py::arg("probs"),
-        py::arg("work") = py::none());
+        py::arg("work") = py::none(), py::arg("label_smoothing") = 0.0);
   m.def("f32_prep_images", &f32_prep_images);
   // test hook: cap every persistent kernel's grid (0 = off) so small-batch oracle tests run
   // the multi-iteration (several tiles per block) paths the benchmark batches run
@@ -1532,7 +1548,8 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("lrn_pool_bwd", &lrn_pool_bwd);
   m.def("softmax_ce", &softmax_ce, py::arg("logits"), py::arg("ldl"), py::arg("labels"), py::arg("B"), py::arg("NC"),
         py::arg("scale"), py::arg("dlogits"), py::arg("ldd"), py::arg("stats"), py::arg("probs"),
-        py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none());
+        py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
+        py::arg("label_smoothing") = 0.0);
   m.def("softmax_ce_dbias_blocks",
         [](int64_t B, int64_t ldl) { return (int64_t)mnistx::softmax_ce_dbias_blocks((int)B, (int)ldl); });
   m.def("splitk_reduce", &splitk_reduce);
@@ -1542,12 +1559,14 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("ce_tail_blocks", [](int64_t nb) { return (int64_t)mnistx::ce_tail_blocks((int)nb); });
   m.def("ce_tail", &ce_tail, py::arg("x"), py::arg("w5t"), py::arg("b5"), py::arg("nc"), py::arg("labels"),
         py::arg("nb"), py::arg("scale"), py::arg("logits"), py::arg("dl") = py::none(), py::arg("dx") = py::none(),
-        py::arg("stats"), py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none());
+        py::arg("stats"), py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
+        py::arg("label_smoothing") = 0.0);
   m.def("mlp_head", &mlp_head, py::arg("x"), py::arg("w3t"), py::arg("b3"), py::arg("n1"), py::arg("w4t"),
         py::arg("b4"), py::arg("n2"), py::arg("w5t"), py::arg("b5"), py::arg("nc"), py::arg("labels"), py::arg("nb"),
         py::arg("scale"), py::arg("h3"), py::arg("h4"), py::arg("logits"), py::arg("dl") = py::none(),
         py::arg("dh4") = py::none(), py::arg("dh3") = py::none(), py::arg("dx") = py::none(), py::arg("stats"),
-        py::arg("work"), py::arg("defer_stats") = false, py::arg("dbias") = py::none());
+        py::arg("work"), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
+        py::arg("label_smoothing") = 0.0);
   m.def("fused_optimizer", &fused_optimizer, py::arg("params"), py::arg("grads"), py::arg("mom"), py::arg("ema"),
         py::arg("bf"), py::arg("segs"), py::arg("step"), py::arg("lr0"), py::arg("decay_rate"),
         py::arg("decay_steps"), py::arg("momentum"), py::arg("nesterov"), py::arg("use_momentum"),

@@ -9,6 +9,20 @@
 
 constexpr int CE_MAXB = 1024;  // max blocks per launch (work holds 4 floats per block + ticket)
 
+// Label smoothing.  The softmax-CE kernels take a compile-time SMOOTH switch; the smoothed
+// instantiation has ONE more trailing kernel argument, eps (a `float` argument pack, empty in the
+// plain instantiation, whose arguments and code therefore stay what they were).  With
+// on = 1 - eps and off = eps / NC (NC = the real class count):
+//   loss = log(se) - on * (l_y - mx) - off * sum_{c < NC} (l_c - mx)
+//   dl_c = (p_c - on * [c == y] - off) * scale
+// The class sum is over the differences, which stay finite for |l_c - mx| <= 1e37.
+template <typename... T>
+DEV float smooth_eps(T... eps) {
+  static_assert(sizeof...(T) <= 1, "one eps at most");
+  if constexpr (sizeof...(T) == 0) return 0.f;
+  else return (eps + ...);
+}
+
 // Every thread of the block must call this (it synchronises the block).
 // With work == nullptr each block adds its partial atomically (order-dependent).
 // defer: only write the block's partial; finalize_k combines them in block order in

@@ -416,11 +416,19 @@ __global__ __launch_bounds__(256) void lrn_f32_bwd_k(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------- softmax cross-entropy, fp32 gradient
+// SMOOTH: label smoothing (ce_stats.h), eps as the one member of the trailing argument pack.
+template <bool SMOOTH = false, typename... EPS>
 __global__ __launch_bounds__(256) void softmax_ce_f32_k(const float* __restrict__ logits, int ldl,
                                                         const int32_t* __restrict__ labels, int B, int NC,
                                                         float scale, float* __restrict__ dl, int ldd,
                                                         float* __restrict__ stats, float* __restrict__ probs,
-                                                        float* __restrict__ work) {
+                                                        float* __restrict__ work, EPS... eps) {
+  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
+  float sm_on = 1.f, sm_off = 0.f;
+  if constexpr (SMOOTH) {
+    sm_on = 1.f - smooth_eps(eps...);
+    sm_off = smooth_eps(eps...) / (float)NC;
+  }
   float loss = 0.f, corr = 0.f, bad = 0.f;
   for (int row = blockIdx.x * 256 + threadIdx.x; row < B; row += gridDim.x * 256) {
     const float* l = logits + (int64_t)row * ldl;
@@ -432,14 +440,26 @@ __global__ __launch_bounds__(256) void softmax_ce_f32_k(const float* __restrict_
     const int lab = labels ? labels[row] : -1;
     if (labels) {
       const float ll = l[lab];
-      const float lo = -(ll - mx - logf(se));
+      float lo;
+      if constexpr (SMOOTH) {
+        float sd = 0.f;
+        for (int c = 0; c < NC; ++c) sd += l[c] - mx;
+        lo = fmaf(-sm_off, sd, fmaf(-sm_on, ll - mx, logf(se)));
+      } else {
+        lo = -(ll - mx - logf(se));
+      }
       loss += lo;
       corr += ll >= mx ? 1.f : 0.f;
       if (!isfinite(lo)) bad = 1.f;
     }
     if (dl)
-      for (int c = 0; c < ldd; ++c)
-        dl[(int64_t)row * ldd + c] = c < NC ? (expf(l[c] - mx) * inv - (c == lab ? 1.f : 0.f)) * scale : 0.f;
+      for (int c = 0; c < ldd; ++c) {
+        if constexpr (SMOOTH)
+          dl[(int64_t)row * ldd + c] =
+              c < NC ? (expf(l[c] - mx) * inv - (c == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
+        else
+          dl[(int64_t)row * ldd + c] = c < NC ? (expf(l[c] - mx) * inv - (c == lab ? 1.f : 0.f)) * scale : 0.f;
+      }
     if (probs)
       for (int c = 0; c < NC; ++c) probs[(int64_t)row * NC + c] = expf(l[c] - mx) * inv;
   }
@@ -800,11 +820,17 @@ hipError_t f32_lrn_pool_bwd(const float* x, const float* dy, const uint8_t* arg,
 }
 
 hipError_t f32_softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale, float* dl,
-                          int ldd, float* stats, float* probs, float* work, hipStream_t st) {
+                          int ldd, float* stats, float* probs, float* work, hipStream_t st, float label_smoothing) {
   int nb = (B + 255) / 256;
   nb = nb < 1 ? 1 : (nb > CE_MAXB ? CE_MAXB : nb);
-  hipLaunchKernelGGL(softmax_ce_f32_k, dim3(nb), dim3(256), 0, st, logits, ldl, labels, B, NC, scale, dl, ldd, stats,
-                     probs, work);
+  if (label_smoothing != 0.f) {
+    if (!labels) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((softmax_ce_f32_k<true, float>), dim3(nb), dim3(256), 0, st, logits, ldl, labels, B, NC, scale, dl,
+                       ldd, stats, probs, work, label_smoothing);
+  } else {
+    hipLaunchKernelGGL(softmax_ce_f32_k<>, dim3(nb), dim3(256), 0, st, logits, ldl, labels, B, NC, scale, dl, ldd, stats,
+                       probs, work);
+  }
   return hipGetLastError();
 }
 

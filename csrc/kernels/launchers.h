@@ -250,7 +250,8 @@ hipError_t f32_lrn_pool_fwd(const float* x, int Nb, int H, int W, int C, int r, 
 hipError_t f32_lrn_pool_bwd(const float* x, const float* dy, const uint8_t* arg, int Nb, int H, int W, int C, int r,
                             float bias, float alpha, float beta, int relu_mask, float* dx, hipStream_t st);
 hipError_t f32_softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale, float* dl,
-                          int ldd, float* stats, float* probs, float* work, hipStream_t st);
+                          int ldd, float* stats, float* probs, float* work, hipStream_t st,
+                          float label_smoothing = 0.f);
 hipError_t f32_prep_images(const uint8_t* src, const int64_t* idx, const int32_t* lab_src, int B, int HW, int Csrc,
                            int Cdst, float* out, int32_t* lab_out, hipStream_t st);
 
@@ -287,9 +288,12 @@ hipError_t lrn_pool_bwd(const bf16_t* x, const bf16_t* dP, const uint8_t* arg, i
 // caller's finalize_step combines them (ce_stats.h defer)
 // dbias (optional, with dlogits): per-block fp32 column sums of dlogits [blocks][ldl]
 // (blocks = softmax_ce_dbias_blocks; only the row kernel, ldl 16 / 32, writes them)
+// label_smoothing (here and on f32_softmax_ce, mlp_head, ce_tail): eps of the smoothed target
+// (1 - eps) * onehot + eps / NC (ce_stats.h).  0 launches the plain instantiation with the plain
+// arguments; any other value the smoothed one (needs labels; the fused heads: the training form)
 hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale,
                       bf16_t* dlogits, int ldd, float* stats, float* probs, float* work, hipStream_t st,
-                      int* defer_blocks = nullptr, float* dbias = nullptr);
+                      int* defer_blocks = nullptr, float* dbias = nullptr, float label_smoothing = 0.f);
 int softmax_ce_dbias_blocks(int B, int ldl);
 // Fused LeNet-5 dense head (mlp_head.hip): fc3/fc4/fc5 + softmax-CE (+ with dl:
 // the data-gradient chain dlogits -> dh4 -> dh3 -> dx).  Writes h3, h4, logits
@@ -299,7 +303,8 @@ bool mlp_head_supported(int d0, int ld1, int ld2, int ld3, int n1, int n2, int n
 hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t, const float* b4,
                     int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
                     bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
-                    float* stats, float* work, hipStream_t st, int defer_stats = 0, float* dbias = nullptr);
+                    float* stats, float* work, hipStream_t st, int defer_stats = 0, float* dbias = nullptr,
+                    float label_smoothing = 0.f);
 // blocks of one mlp_head launch (its per-block CE partials when defer_stats is set)
 int mlp_head_blocks(int nb);
 // the reference CNN's softmax_linear (192 -> nc <= 16) + softmax CE + its data gradient (masked by
@@ -309,7 +314,18 @@ bool ce_tail_supported(int d0, int nc, int B);
 int ce_tail_blocks(int nb);
 hipError_t ce_tail(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
                    float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                   int defer_stats, float* dbias);
+                   int defer_stats, float* dbias, float label_smoothing = 0.f);
+// the smoothed instantiations (mlp_head_smooth.hip), which mlp_head / ce_tail call for
+// label_smoothing != 0: the gradient form only (dl required)
+int ce_tail_nw(int nb);
+hipError_t ce_tail_smooth(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
+                          float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work,
+                          hipStream_t st, int defer_stats, float* dbias, float label_smoothing);
+hipError_t mlp_head_smooth(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
+                           const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
+                           int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
+                           bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
+                           float* dbias, float label_smoothing);
 // NOTE: many splits over a small output are pre-summed IN PLACE (the slab is scratch).
 hipError_t splitk_reduce(float* slab, int splits, int M, int N, int G, int Ipad, int I, int J,
                          int bias_row, float* wdst, float* bdst, float scale, hipStream_t st);

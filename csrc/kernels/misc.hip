@@ -526,9 +526,17 @@ __global__ __launch_bounds__(TPB) void lrn_pool14_bwd_k(const bf16_t* __restrict
 
 // ------------------------------------------------------------------ K8 softmax cross-entropy
 // stats[0] += sum(-log p[label]) ; stats[1] += #(logit[label] == max) ; stats[2] = 1 if non-finite.
+// SMOOTH: label smoothing (ce_stats.h), eps as the one member of the trailing argument pack.
+template <bool SMOOTH = false, typename... EPS>
 __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ labels, int B,
                              int NC, float scale, bf16_t* __restrict__ dl, int ldd, float* __restrict__ stats,
-                             float* __restrict__ probs) {
+                             float* __restrict__ probs, EPS... eps) {
+  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
+  float sm_on = 1.f, sm_off = 0.f;
+  if constexpr (SMOOTH) {
+    sm_on = 1.f - smooth_eps(eps...);
+    sm_off = smooth_eps(eps...) / (float)NC;
+  }
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   float loss = 0.f, corr = 0.f;
   int bad = 0;
@@ -542,7 +550,13 @@ __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const in
     const int lab = labels ? labels[row] : -1;
     if (labels) {
       const float ll = l[lab];
-      loss = -(ll - mx - __logf(se));
+      if constexpr (SMOOTH) {
+        float sd = 0.f;
+        for (int c = 0; c < NC; ++c) sd += l[c] - mx;
+        loss = fmaf(-sm_off, sd, fmaf(-sm_on, ll - mx, __logf(se)));
+      } else {
+        loss = -(ll - mx - __logf(se));
+      }
       corr = (ll >= mx) ? 1.f : 0.f;
       if (!isfinite(loss)) bad = 1;
     }
@@ -550,7 +564,11 @@ __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const in
       bf16_t* d = dl + (int64_t)row * ldd;
       for (int c = 0; c < ldd; ++c) {
         float g = 0.f;
-        if (c < NC) g = (__expf(l[c] - mx) * inv - (c == lab ? 1.f : 0.f)) * scale;
+        if constexpr (SMOOTH) {
+          if (c < NC) g = (__expf(l[c] - mx) * inv - (c == lab ? sm_on + sm_off : sm_off)) * scale;
+        } else {
+          if (c < NC) g = (__expf(l[c] - mx) * inv - (c == lab ? 1.f : 0.f)) * scale;
+        }
         d[c] = f2bf(g);
       }
     }
@@ -574,13 +592,19 @@ __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const in
 // 16-byte bf16 stores.  Statistics: warp + block reduction, then either one
 // atomic per block or -- with a workspace -- per-block partials combined by the
 // last block to finish (ticket counter) in block order: bitwise deterministic.
-template <int LD>
+template <int LD, bool SMOOTH = false, typename... EPS>
 __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict__ logits,
                                                          const int32_t* __restrict__ labels, int B, int NC,
                                                          float scale, bf16_t* __restrict__ dl,
                                                          float* __restrict__ stats, float* __restrict__ probs,
                                                          float* __restrict__ work, int defer_stats,
-                                                         float* __restrict__ dbias) {
+                                                         float* __restrict__ dbias, EPS... eps) {
+  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
+  float sm_on = 1.f, sm_off = 0.f;
+  if constexpr (SMOOTH) {
+    sm_on = 1.f - smooth_eps(eps...);
+    sm_off = smooth_eps(eps...) / (float)NC;
+  }
   float loss = 0.f, corr = 0.f, bad = 0.f;
   float cs[LD];   // fp32 column sums of dlogits (dbias: the last layer's bias gradient partial)
 #pragma unroll
@@ -611,7 +635,16 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
       float ll = 0.f;
 #pragma unroll
       for (int c = 0; c < LD; ++c) ll = (c == lab) ? l[c] : ll;
-      const float lo = -(ll - mx - __logf(se));
+      float lo;
+      if constexpr (SMOOTH) {
+        float sd = 0.f;
+#pragma unroll
+        for (int c = 0; c < LD; ++c)
+          if (c < NC) sd += l[c] - mx;
+        lo = fmaf(-sm_off, sd, fmaf(-sm_on, ll - mx, __logf(se)));
+      } else {
+        lo = -(ll - mx - __logf(se));
+      }
       loss += lo;
       corr += (ll >= mx) ? 1.f : 0.f;
       if (!isfinite(lo)) bad = 1.f;
@@ -623,8 +656,14 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
           const int c0 = 8 * v + 2 * h;
-          const float g0 = c0 < NC ? (e[c0] * inv - (c0 == lab ? 1.f : 0.f)) * scale : 0.f;
-          const float g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - (c0 + 1 == lab ? 1.f : 0.f)) * scale : 0.f;
+          float g0, g1;
+          if constexpr (SMOOTH) {
+            g0 = c0 < NC ? (e[c0] * inv - (c0 == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
+            g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - (c0 + 1 == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
+          } else {
+            g0 = c0 < NC ? (e[c0] * inv - (c0 == lab ? 1.f : 0.f)) * scale : 0.f;
+            g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - (c0 + 1 == lab ? 1.f : 0.f)) * scale : 0.f;
+          }
           o[h] = pack2(g0, g1);
           cs[c0] += g0;
           cs[c0 + 1] += g1;
@@ -1699,15 +1738,23 @@ int softmax_ce_dbias_blocks(int B, int ldl) {
 
 hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale,
                       bf16_t* dlogits, int ldd, float* stats, float* probs, float* work, hipStream_t st,
-                      int* defer_blocks, float* dbias) {
+                      int* defer_blocks, float* dbias, float label_smoothing) {
   const int nb = (int)std::min<int64_t>(CE_MAXB, ((int64_t)B + 255) / 256);
+  const bool smooth = label_smoothing != 0.f;   // the smoothed instantiations, eps as their last argument
+  if (smooth && !labels) return hipErrorInvalidValue;
   if (defer_blocks) *defer_blocks = 0;
   const bool rows_ok = (ldl == 16 || ldl == 32) && NC <= ldl && (!dlogits || ldd == ldl) &&
                        ((uintptr_t)logits % 16 == 0) && (!dlogits || (uintptr_t)dlogits % 16 == 0);
   if (rows_ok && B > 0) {
     const int defer = (defer_blocks && work && stats) ? 1 : 0;
     if (defer) *defer_blocks = nb;
-    if (ldl == 16)
+    if (smooth && ldl == 16)
+      hipLaunchKernelGGL((softmax_ce_rows_k<16, true, float>), dim3(nb), dim3(256), 0, st, logits, labels, B, NC, scale,
+                         dlogits, stats, probs, work, defer, dbias, label_smoothing);
+    else if (smooth)
+      hipLaunchKernelGGL((softmax_ce_rows_k<32, true, float>), dim3(nb), dim3(256), 0, st, logits, labels, B, NC, scale,
+                         dlogits, stats, probs, work, defer, dbias, label_smoothing);
+    else if (ldl == 16)
       hipLaunchKernelGGL(softmax_ce_rows_k<16>, dim3(nb), dim3(256), 0, st, logits, labels, B, NC, scale, dlogits,
                          stats, probs, work, defer, dbias);
     else
@@ -1716,8 +1763,12 @@ hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B
     return hipGetLastError();
   }
   if (dbias) return hipErrorInvalidValue;   // the row kernel's block partials only
-  hipLaunchKernelGGL(softmax_ce_k, dim3((B + TPB - 1) / TPB), dim3(TPB), 0, st, logits, ldl, labels, B, NC, scale,
-                     dlogits, ldd, stats, probs);
+  if (smooth)
+    hipLaunchKernelGGL((softmax_ce_k<true, float>), dim3((B + TPB - 1) / TPB), dim3(TPB), 0, st, logits, ldl, labels, B,
+                       NC, scale, dlogits, ldd, stats, probs, label_smoothing);
+  else
+    hipLaunchKernelGGL(softmax_ce_k<>, dim3((B + TPB - 1) / TPB), dim3(TPB), 0, st, logits, ldl, labels, B, NC, scale,
+                       dlogits, ldd, stats, probs);
   return hipGetLastError();
 }
 

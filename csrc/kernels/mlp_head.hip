@@ -164,11 +164,25 @@ DEV void dx_tiles(int v0, const bf16_t* i3, const uint32_t (&d3p)[T1][8], bf16_t
   }
 }
 
+// The smoothed loss of a row whose classes (i&3) + 8(i>>2) + 4h live in lanes r and r + 32
+// (ce_stats.h): the masked class sum of l_c - mx, joined across the two half-rows as se and ll are.
+// Both lanes of a row must call it.
+DEV float smooth_loss(const float (&lg)[8], float mx, float se, float ll, int h, int nc, float eps) {
+  const float off = eps / (float)nc, on = 1.f - eps;
+  float sd = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    if ((i & 3) + 8 * (i >> 2) + 4 * h < nc) sd += lg[i] - mx;
+  sd += __shfl_xor(sd, 32, 64);
+  return fmaf(-off, sd, fmaf(-on, ll - mx, __logf(se)));
+}
+
 // NW waves per block, TPW 32-row tiles per wave.  The launch uses TPW = 1 (every wave's
 // load / compute / store phases in lockstep); TPW = 2 with 4 waves (the next tile's X
 // loads under the current tile's backward chain) measured slower (0.540 vs 0.53 ms/step,
 // profiles/r3/lenet/knobs/).
-template <bool GRADS, int NW = NWAVE, int TPW = 1>
+// SMOOTH: label smoothing (ce_stats.h), eps as the one member of the trailing argument pack.
+template <bool GRADS, int NW = NWAVE, int TPW = 1, bool SMOOTH = false, typename... EPS>
 __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W3t,
                                                   const float* __restrict__ b3, int n1, const bf16_t* __restrict__ W4t,
                                                   const float* __restrict__ b4, int n2, const bf16_t* __restrict__ W5t,
@@ -179,7 +193,8 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
                                                   bf16_t* __restrict__ dh4, bf16_t* __restrict__ dh3,
                                                   bf16_t* __restrict__ dx, float* __restrict__ stats,
                                                   float* __restrict__ work, int defer_stats,
-                                                  float* __restrict__ dbias) {
+                                                  float* __restrict__ dbias, EPS... eps) {
+  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
   __shared__ __attribute__((aligned(16))) bf16_t i3[R3 * S3];
   __shared__ __attribute__((aligned(16))) bf16_t i4[R4 * S4];
   __shared__ __attribute__((aligned(16))) bf16_t i5[R5 * S5];
@@ -337,7 +352,14 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) ll = ((i & 3) + 8 * (i >> 2) + 4 * h == lab) ? lg[i] : ll;
     ll += __shfl_xor(ll, 32, 64);
-    if (valid && h == 0) {
+    if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
+      const float lo = smooth_loss(lg, mx, se, ll, h, nc, smooth_eps(eps...));   // by both half-rows
+      if (valid && h == 0) {
+        loss += lo;
+        corr += (ll >= mx) ? 1.f : 0.f;
+        bad = isfinite(lo) ? bad : 1.f;
+      }
+    } else if (valid && h == 0) {
       const float lo = -(ll - mx - __logf(se));
       loss += lo;
       corr += (ll >= mx) ? 1.f : 0.f;
@@ -352,7 +374,12 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int i = 2 * w + k, cls = (i & 3) + 8 * (i >> 2) + 4 * h;
-          g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? 1.f : 0.f)) * scale : 0.f;
+          if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
+            const float off = smooth_eps(eps...) / (float)nc, on = 1.f - smooth_eps(eps...);
+            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? on + off : off)) * scale : 0.f;
+          } else {
+            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? 1.f : 0.f)) * scale : 0.f;
+          }
           cs[i] += valid ? g2[k] : 0.f;
         }
         dlp[w] = pack2(g2[0], g2[1]);
@@ -461,14 +488,15 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
 constexpr int TD0 = 192, TK = TD0 / 16, TU = TD0 / 32;
 DEV int toff(int r, int col) { return r * TD0 + ((((col >> 3) ^ ((r >> 2) & 3)) << 3) | (col & 7)); }
 
-template <int TNW, bool GRADS>
+template <int TNW, bool GRADS, bool SMOOTH = false, typename... EPS>
 __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W5t,
                                                      const float* __restrict__ b5, int nc,
                                                      const int32_t* __restrict__ labels, int nb, float scale,
                                                      float* __restrict__ logits, bf16_t* __restrict__ dl,
                                                      bf16_t* __restrict__ dx, float* __restrict__ stats,
                                                      float* __restrict__ work, int defer_stats,
-                                                     float* __restrict__ dbias) {
+                                                     float* __restrict__ dbias, EPS... eps) {
+  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
   __shared__ __attribute__((aligned(16))) bf16_t i5[16 * TD0];
   __shared__ __attribute__((aligned(16))) float bias5[LD3];
   __shared__ __attribute__((aligned(16))) bf16_t stage[TNW * STG];
@@ -535,7 +563,14 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) ll = ((i & 3) + 8 * (i >> 2) + 4 * h == lab) ? lg[i] : ll;
     ll += __shfl_xor(ll, 32, 64);
-    if (valid && h == 0) {
+    if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
+      const float lo = smooth_loss(lg, mx, se, ll, h, nc, smooth_eps(eps...));   // by both half-rows
+      if (valid && h == 0) {
+        loss += lo;
+        corr += (ll >= mx) ? 1.f : 0.f;
+        bad = isfinite(lo) ? bad : 1.f;
+      }
+    } else if (valid && h == 0) {
       const float lo = -(ll - mx - __logf(se));
       loss += lo;
       corr += (ll >= mx) ? 1.f : 0.f;
@@ -550,7 +585,12 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int i = 2 * w + k, cls = (i & 3) + 8 * (i >> 2) + 4 * h;
-          g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? 1.f : 0.f)) * scale : 0.f;
+          if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
+            const float off = smooth_eps(eps...) / (float)nc, on = 1.f - smooth_eps(eps...);
+            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? on + off : off)) * scale : 0.f;
+          } else {
+            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? 1.f : 0.f)) * scale : 0.f;
+          }
           cs[i] += valid ? g2[k] : 0.f;
         }
         dlp[w] = pack2(g2[0], g2[1]);
@@ -603,6 +643,42 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
 
 }  // namespace
 
+#ifdef MNISTX_HEAD_SMOOTH_TU
+// mlp_head_smooth.hip: the smoothed instantiations alone, as a translation unit of their own.  In
+// one module with them the plain mlp_head_k<true> came out of the compiler with other address
+// arithmetic and registers (4306 instead of 4290 instructions); apart, this file's code object
+// is what it was before the smoothed kernels existed.
+hipError_t ce_tail_smooth(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
+                          float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work,
+                          hipStream_t st, int defer_stats, float* dbias, float label_smoothing) {
+  if (nb <= 0) return hipSuccess;
+  if (!dl) return hipErrorInvalidValue;   // a training quantity: the gradient form only
+  const dim3 grid(ce_tail_blocks(nb));
+  const int nw = ce_tail_nw(nb);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(64 * nw), 0, st, x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats,
+                       work, defer_stats, dbias, label_smoothing);
+  };
+  if (nw == 1) go(ce_tail_k<1, true, true, float>);
+  else if (nw == 2) go(ce_tail_k<2, true, true, float>);
+  else go(ce_tail_k<4, true, true, float>);
+  return hipGetLastError();
+}
+
+hipError_t mlp_head_smooth(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
+                           const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
+                           int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
+                           bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
+                           float* dbias, float label_smoothing) {
+  if (nb <= 0) return hipSuccess;
+  if (!dl) return hipErrorInvalidValue;
+  const dim3 grid((nb + ROWS - 1) / ROWS);
+  hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float>), grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4, n2,
+                     w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work, defer_stats, dbias,
+                     label_smoothing);
+  return hipGetLastError();
+}
+#else
 // waves per block (32 rows each): 2, or more when the block count would exceed the CE partial
 // slots; MNISTX_CE_TAIL_NW overrides (1, 2 or 4).  At B = 16384 2 waves (256 blocks) measured
 // 9.9 us, 1 wave 11.6 us, 4 waves 10.9 us (profiles/r6/cetail/README.md)
@@ -621,7 +697,10 @@ bool ce_tail_supported(int d0, int nc, int B) { return d0 == TD0 && nc > 0 && nc
 
 hipError_t ce_tail(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
                    float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                   int defer_stats, float* dbias) {
+                   int defer_stats, float* dbias, float label_smoothing) {
+  if (label_smoothing != 0.f)
+    return ce_tail_smooth(x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats, work, st, defer_stats, dbias,
+                          label_smoothing);
   if (nb <= 0) return hipSuccess;
   const dim3 grid(ce_tail_blocks(nb));
   const int nw = ce_tail_nw(nb);
@@ -651,7 +730,10 @@ bool mlp_head_supported(int d0, int ld1, int ld2, int ld3, int n1, int n2, int n
 hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t, const float* b4,
                     int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
                     bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
-                    float* stats, float* work, hipStream_t st, int defer_stats, float* dbias) {
+                    float* stats, float* work, hipStream_t st, int defer_stats, float* dbias, float label_smoothing) {
+  if (label_smoothing != 0.f)
+    return mlp_head_smooth(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3,
+                           dx, stats, work, st, defer_stats, dbias, label_smoothing);
   if (nb <= 0) return hipSuccess;
   const dim3 grid((nb + ROWS - 1) / ROWS);   // ROWS rows per block
   if (dl)
@@ -662,5 +744,6 @@ hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1,
                        scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work, defer_stats, nullptr);
   return hipGetLastError();
 }
+#endif
 
 }  // namespace mnistx

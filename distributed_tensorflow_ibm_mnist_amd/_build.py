@@ -92,7 +92,10 @@ def build_kernels(force: bool = False, verbose: bool = True, jobs: int = 8) -> s
     for s in hip_srcs:
         o = os.path.join(BUILD, os.path.basename(s) + ".o")
         objs.append(o)
-        if force or _newer(o, [s] + hdrs):
+        # a unit may compile another unit's kernel text (mlp_head_smooth.hip includes mlp_head.hip)
+        with open(s) as f:
+            incl = [os.path.join(kdir, ln.split('"')[1]) for ln in f if ln.startswith('#include "') and ".hip" in ln]
+        if force or _newer(o, [s] + incl + hdrs):
             # MFMA accumulators in the VGPR form: the AGPR form made the register allocator
             # shuffle loop-carried accumulators with v_accvgpr moves (up to 12 per step)
             jobs_list.append([HIPCC, "-std=c++17", "-O3", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-fPIC",

@@ -105,14 +105,15 @@ def forward(spec: ModelSpec, params: Dict[str, torch.Tensor], x: torch.Tensor,
 
 
 def losses(spec: ModelSpec, params: Dict[str, torch.Tensor], logits: torch.Tensor,
-           labels: torch.Tensor) -> Dict[str, torch.Tensor]:
-    """All entries of the reference 'losses' collection plus total_loss."""
+           labels: torch.Tensor, label_smoothing: float = 0.0) -> Dict[str, torch.Tensor]:
+    """All entries of the reference 'losses' collection plus total_loss (``label_smoothing``:
+    the training form of ``cross_entropy``, against (1 - eps) * onehot + eps / classes)."""
     out: Dict[str, torch.Tensor] = {}
     for L in spec.weights():
         if L.wd is not None:
             wgt = params[f"{L.name}/weights"]
             out[f"{L.name}/weight_loss"] = float(L.wd) * 0.5 * (wgt * wgt).sum()
-    out["cross_entropy"] = F.cross_entropy(logits, labels.long())
+    out["cross_entropy"] = F.cross_entropy(logits, labels.long(), label_smoothing=label_smoothing)
     out["total_loss"] = sum(out.values())
     return out
 

@@ -166,13 +166,15 @@ class LRNFn(torch.autograd.Function):
 
 class SoftmaxCrossEntropyFn(torch.autograd.Function):
     """Mean sparse softmax cross-entropy; the same kernel pass produces dlogits,
-    the top-1 correct count and a non-finite flag (returned as ``stats``)."""
+    the top-1 correct count and a non-finite flag (returned as ``stats``).  With
+    ``label_smoothing`` the loss (and stats[0]) is the smoothed one."""
 
     @staticmethod
-    def forward(ctx, logits, labels, n_classes: int):
+    def forward(ctx, logits, labels, n_classes: int, label_smoothing: float = 0.0):
         logits = logits.float().contiguous()
         B = logits.shape[0]
-        dl, stats = Fk.softmax_ce(logits, labels.to(torch.int32).contiguous(), n_classes, scale=1.0 / B)
+        dl, stats = Fk.softmax_ce(logits, labels.to(torch.int32).contiguous(), n_classes, scale=1.0 / B,
+                                  label_smoothing=label_smoothing)
         ctx.save_for_backward(dl)
         ctx.mark_non_differentiable(stats)
         return stats[0] / B, stats
@@ -180,7 +182,7 @@ class SoftmaxCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dstats):
         (dl,) = ctx.saved_tensors
-        return dl.float() * dloss, None, None
+        return dl.float() * dloss, None, None, None
 
 
 def conv2d(x, w, b=None, padding: str = "SAME", relu: bool = True, cout_pad: Optional[int] = None):
@@ -204,6 +206,6 @@ def lrn(x, r: int = 4, bias: float = 1.0, alpha: float = 0.001 / 9.0, beta: floa
     return LRNFn.apply(x, r, bias, alpha, beta)
 
 
-def softmax_cross_entropy(logits, labels, n_classes: int):
+def softmax_cross_entropy(logits, labels, n_classes: int, label_smoothing: float = 0.0):
     """Returns (mean loss, stats f32[8]: [sum CE, #correct, nonfinite flag, ...])."""
-    return SoftmaxCrossEntropyFn.apply(logits, labels, n_classes)
+    return SoftmaxCrossEntropyFn.apply(logits, labels, n_classes, label_smoothing)

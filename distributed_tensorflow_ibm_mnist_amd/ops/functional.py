@@ -272,8 +272,9 @@ def lrn_bwd(x: torch.Tensor, dy: torch.Tensor, r: int, bias: float, alpha: float
 
 def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, n_classes: int, scale: Optional[float] = None,
                dlogits: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
-               want_grad: bool = True):
-    """Fused softmax-CE fwd+bwd.  Returns (dlogits bf16 [B, ld] or None, stats f32[8])."""
+               want_grad: bool = True, label_smoothing: float = 0.0):
+    """Fused softmax-CE fwd+bwd.  Returns (dlogits bf16 [B, ld] or None, stats f32[8]).
+    ``label_smoothing`` eps: loss and gradient against (1 - eps) * onehot + eps / n_classes."""
     B, ld = logits.shape
     if scale is None:
         scale = 1.0 / B
@@ -281,7 +282,8 @@ def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, n_classes: int, scale
         stats = torch.zeros(8, dtype=torch.float32, device=logits.device)
     if want_grad and dlogits is None:
         dlogits = torch.empty(B, ld, dtype=torch.bfloat16, device=logits.device)
-    kernels().softmax_ce(logits, ld, labels, B, n_classes, scale, dlogits if want_grad else None, ld, stats, None)
+    kernels().softmax_ce(logits, ld, labels, B, n_classes, scale, dlogits if want_grad else None, ld, stats, None,
+                         label_smoothing=label_smoothing)
     return dlogits, stats
 
 

@@ -71,13 +71,15 @@ class Linear(nn.Module):
 
 
 class SoftmaxCrossEntropy(nn.Module):
-    def __init__(self, n_classes: int):
+    def __init__(self, n_classes: int, label_smoothing: float = 0.0):
         super().__init__()
-        self.n_classes = n_classes
+        if not 0 <= float(label_smoothing) < 1:      # NaN fails both comparisons
+            raise ValueError(f"label_smoothing must be finite with 0 <= label_smoothing < 1, got {label_smoothing}")
+        self.n_classes, self.label_smoothing = n_classes, float(label_smoothing)
         self.last_stats: Optional[torch.Tensor] = None
 
     def forward(self, logits, labels):
-        loss, stats = A.softmax_cross_entropy(logits, labels, self.n_classes)
+        loss, stats = A.softmax_cross_entropy(logits, labels, self.n_classes, self.label_smoothing)
         self.last_stats = stats
         return loss
 

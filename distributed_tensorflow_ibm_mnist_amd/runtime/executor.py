@@ -645,12 +645,15 @@ class HipNet:
         # training statistics: the per-block CE partials are combined by this step's
         # finalize_k (no agent-scope fence / ticket inside the head; ce_stats.h)
         defer = grads and stats is self.stats and self.ce_work is not None
+        # label smoothing shapes the training loss alone: the eval form keeps the hard labels
+        eps = self.opt.label_smoothing if grads else 0.0
         if self.head_kind == "tail":
             l5 = self.layers[i]
             K = kernels()
             K.ce_tail(l5.x, self.fp.bf16t_view(l5.wname), self.fp.param_view(l5.bname), l5.spec.dout, self.labels,
                       nb, scale, l5.out, dl=self.dlogits if grads else None, dx=self.dbuf[i] if grads else None,
-                      stats=stats, work=self.ce_work, defer_stats=defer, dbias=self.ce_dbias if grads else None)
+                      stats=stats, work=self.ce_work, defer_stats=defer, dbias=self.ce_dbias if grads else None,
+                      label_smoothing=eps)
             if grads:
                 l5.ce_bias = (self.ce_dbias, K.ce_tail_blocks(nb))
             if defer:
@@ -665,7 +668,7 @@ class HipNet:
                            dl=self.dlogits if grads else None, dh4=self.dbuf[i + 2] if grads else None,
                            dh3=self.dbuf[i + 1] if grads else None, dx=self.dbuf[i] if grads else None,
                            stats=stats, work=self.ce_work, defer_stats=defer,
-                           dbias=self.ce_dbias if grads else None)
+                           dbias=self.ce_dbias if grads else None, label_smoothing=eps)
         if grads:
             l5.ce_bias = (self.ce_dbias, kernels().mlp_head_blocks(nb))
         if defer:
@@ -775,7 +778,7 @@ class HipNet:
             self.logits, ld, self.labels, nb, self.n_classes,
             (1.0 / nb) if scale is None else scale, self.dlogits, ld, self.stats,
             None, self.ce_work, defer_stats=self.ce_work is not None,
-            dbias=self.ce_dbias if nblk > 0 else None)
+            dbias=self.ce_dbias if nblk > 0 else None, label_smoothing=self.opt.label_smoothing)
         self.layers[-1].ce_bias = (self.ce_dbias, nblk) if nblk > 0 else None
 
     def backward(self, nb: Optional[int] = None) -> None:

@@ -372,7 +372,7 @@ class HipNetF32:
         nb = self.B if nb is None else nb
         kernels().f32_softmax_ce(self.logits, self.logits.shape[1], self.labels, nb, self.n_classes,
                                  (1.0 / nb) if scale is None else scale, self.dlogits, self.logits.shape[1],
-                                 self.stats, None, self.ce_work)
+                                 self.stats, None, self.ce_work, label_smoothing=self.opt.label_smoothing)
 
     def backward(self, nb: Optional[int] = None) -> None:
         nb = self.B if nb is None else nb

@@ -68,8 +68,22 @@ class OptConfig:
     total_steps: int = 0          # polynomial | cosine: > warmup_steps
     lr_end: float = 0.0
     lr_power: float = 1.0         # polynomial
+    # the training loss is the cross-entropy against (1 - eps) * onehot + eps / classes (the
+    # softmax-CE kernels' smoothed instantiations); eval paths keep the hard labels.  Not an
+    # optimizer quantity, but OptConfig is the nets' one training-config channel.
+    label_smoothing: float = 0.0
 
     def __post_init__(self):
+        try:
+            if isinstance(self.label_smoothing, bool):
+                raise ValueError
+            self.label_smoothing = float(self.label_smoothing)
+        except (TypeError, ValueError):
+            raise ValueError(f"label_smoothing must be a number with 0 <= label_smoothing < 1, "
+                             f"got {self.label_smoothing!r}") from None
+        if not 0 <= self.label_smoothing < 1:     # NaN fails both comparisons
+            raise ValueError(f"label_smoothing must be finite with 0 <= label_smoothing < 1, "
+                             f"got {self.label_smoothing}")
         self.schedule = str(self.schedule).lower()
         if self.schedule not in LR_SCHEDULES:
             raise ValueError(f"schedule must be one of {'|'.join(LR_SCHEDULES)}, got {self.schedule!r}")
@@ -108,8 +122,10 @@ class OptConfig:
             raise ValueError("adagrad_initial_accumulator must be > 0")   # as TF1 requires
 
     @staticmethod
-    def from_spec(spec, decay_steps: int, decay_rate: float, ema: float = 0.9999) -> "OptConfig":
-        """From a parameter-manager ``OptimizerSpec``."""
+    def from_spec(spec, decay_steps: int, decay_rate: float, ema: float = 0.9999,
+                  label_smoothing: float = 0.0) -> "OptConfig":
+        """From a parameter-manager ``OptimizerSpec`` (which does not carry ``label_smoothing``:
+        the caller passes ``getLabelSmoothing()``)."""
         lr = spec.learning_rate
         adaptive = spec.name in ADAPTIVE_RULES + LAYERWISE_RULES
         return OptConfig(lr0=float(lr), decay_rate=float(decay_rate), decay_steps=int(decay_steps),
@@ -124,7 +140,8 @@ class OptConfig:
                          schedule=getattr(spec, "lr_schedule", "staircase"),
                          warmup_steps=getattr(spec, "warmup_steps", 0),
                          total_steps=getattr(spec, "lr_total_steps", 0),
-                         lr_end=getattr(spec, "lr_end", 0.0), lr_power=getattr(spec, "lr_power", 1.0))
+                         lr_end=getattr(spec, "lr_end", 0.0), lr_power=getattr(spec, "lr_power", 1.0),
+                         label_smoothing=label_smoothing)
 
     @property
     def scheduled(self) -> bool:

@@ -179,7 +179,8 @@ class TorchNet:
         if self._leaf is None or not self._leaf.requires_grad:
             self.forward(nb, grad=True)
         lab = self.labels[:nb].long()
-        loss = F.cross_entropy(self._logits, lab, reduction="sum")
+        # the training loss (and its cross_entropy scalar) is the smoothed one; eval_batch is not
+        loss = F.cross_entropy(self._logits, lab, reduction="sum", label_smoothing=self.opt.label_smoothing)
         with torch.no_grad():
             self.stats[0] += loss.detach()
             self.stats[1] += _in_top1(self._logits, lab)

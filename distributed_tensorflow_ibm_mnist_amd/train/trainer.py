@@ -104,7 +104,7 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
     spec = models.get_model(FLAGS.model, FLAGS.in_channels)
     lr0 = pm.getBaseLearningRate()
     opt = OptConfig.from_spec(pm.getOptimizer(lr0), decay_steps_for(batch_size), pm.getLearningRateDecay(),
-                              MOVING_AVERAGE_DECAY)
+                              MOVING_AVERAGE_DECAY, label_smoothing=pm.getLabelSmoothing())
     init = torch_ref.init_params(spec, seed=FLAGS.seed)
     if cl.mode == "ps" and cl.job_name == "ps":
         from ..ckpt.saver import Saver, latest_checkpoint

@@ -16,6 +16,7 @@ overrides:
     getTestData()            -> list[str]
     getValData()             -> list[str]
     getOptimizer(lr)         -> OptimizerSpec
+    getLabelSmoothing()      -> float   (eps of the smoothed training targets; 0.0: hard labels)
 
 Defaults are the TF CIFAR-10 tutorial values that ``mnist_input.py`` mirrors
  — they are *chosen* defaults, not numbers the reference
@@ -53,6 +54,7 @@ DEFAULTS: Dict[str, Any] = {
     "lr_total_steps": None,      # polynomial | cosine: the step at which lr_end is reached; None: max_steps
     "lr_end": 0.0,               # polynomial | cosine: the rate from lr_total_steps on
     "lr_power": 1.0,             # polynomial: the exponent
+    "label_smoothing": 0.0,      # training loss against (1 - eps) * onehot + eps / classes; 0: hard labels
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -137,7 +139,7 @@ def configure(source: Union[None, str, Dict[str, Any]] = None, **overrides: Any)
 FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", "optimizer", "momentum",
              "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
              "adagrad_initial_accumulator", "clip_norm", "lars_eta", "lr_schedule", "warmup_steps",
-             "lr_total_steps", "lr_end", "lr_power")
+             "lr_total_steps", "lr_end", "lr_power", "label_smoothing")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
@@ -234,6 +236,21 @@ def getLrPower() -> float:
     if not (p > 0 and p != float("inf")):
         raise ValueError(f"lr_power must be finite and > 0, got {p}")
     return p
+
+
+def getLabelSmoothing() -> float:
+    """The ``label_smoothing`` key: finite, 0 <= eps < 1.  It shapes the training loss only (the
+    workers compute it, so parameter-server mode takes it as it is) and is no optimizer state."""
+    v = get("label_smoothing")
+    try:
+        if isinstance(v, bool):
+            raise ValueError
+        eps = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"label_smoothing must be a number with 0 <= label_smoothing < 1, got {v!r}") from None
+    if not 0 <= eps < 1:       # NaN fails both comparisons
+        raise ValueError(f"label_smoothing must be finite with 0 <= label_smoothing < 1, got {eps}")
+    return eps
 
 
 def check_ps_lr_schedule(job_name: str, log=print) -> None:

@@ -57,6 +57,8 @@ flags.DEFINE_integer("warmup_steps", -1, "linear warmup (step + 1) / warmup_step
 flags.DEFINE_integer("lr_total_steps", -1, "polynomial | cosine: the step at which --lr_end is reached (max_steps)")
 flags.DEFINE_float("lr_end", -1, "polynomial | cosine: the rate from --lr_total_steps on (0.0)")
 flags.DEFINE_float("lr_power", -1, "polynomial: the exponent (1.0)")
+flags.DEFINE_float("label_smoothing", -1, "train against (1 - eps) * onehot + eps / classes, 0 <= eps < 1 (0.0: hard "
+                   "labels); the training cross_entropy / total_loss are the smoothed loss, every eval stays plain")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
