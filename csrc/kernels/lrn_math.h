@@ -18,9 +18,20 @@ DEV float dpp_from_right(float v) {  // lane i <- lane i+1 within its 16-lane ro
 }
 
 // running window sums of an 8-channel vector: e = R left neighbours, the 8 values, R right
-// neighbours (zeros past the pixel's channels).  One full sum, then +entering -leaving (the
-// inputs are non-negative squares or same-scale products, so the running form loses nothing
-// at bf16 output).  Every LRN kernel sums through this, in this order.
+// neighbours (zeros past the pixel's channels).  One full sum, then +entering -leaving.  Every
+// LRN kernel sums through this, in this order.
+// What the running form loses, against a float64 reference and in units of 2^-23 of the
+// scale of the element's own terms (a float32 transcription, tests/lrn_oracle.py; the kernels
+// are held to 5x these figures plus the bf16 half-ulp, 2^-9 .. 2^-8 = 32768 .. 65536 units):
+//   alpha * max x^2 <= 8 over the tensor (the model's alpha = 0.001 / 9 up to |x| = 268, alpha
+//   = 0.05 up to |x| = 12.6): at most 5 units in the forward and 120 in the backward, a 270th
+//   of a bf16 half-ulp.  A direct sum stays below 4.
+//   outside it (one 128 among values near 0.25 at alpha = 0.05, alpha * max x^2 = 819): the sum
+//   that has held 128^2 keeps an absolute error of ~2^-10 after the 128 left the window; up to
+//   2100 units forward and 38000 backward, more than half of a bf16 half-ulp.
+//   A gradient that is zero at most channels (un-pooled through argmax codes): an element
+//   whose own window holds no term comes out as a rounding residue of its vector's other
+//   terms, ~1e-8 of them, where a direct sum gives 0.
 template <int R, class T>
 DEV void window_sums_e(const T (&e)[8 + 2 * R], T (&s)[8]) {
   // never fused with the multiplies that produced e (squares, products): every caller then
