@@ -858,6 +858,88 @@ void grad_global_norm(Tensor params, Tensor grads, Tensor segs, double grad_scal
          "grad_global_norm");
 }
 
+// The exponent start table of a limits tensor (summary.hip), built from its host copy once: the
+// order and size checks and the one download happen when a tensor (or a changed version of it) is
+// first seen.  An entry holds its limits tensor, so the address cannot be reused while it is cached.
+struct SummaryLimits {
+  Tensor limits, start;
+  uint32_t version;
+};
+Tensor summary_start(const Tensor& limits) {
+  // never destroyed: device tensors must not be freed after the runtime has shut down
+  static std::vector<SummaryLimits>& cache = *new std::vector<SummaryLimits>();
+  const bool versioned = !limits.is_inference();   // an inference tensor has no version: checked every time
+  const uint32_t ver = versioned ? limits._version() : 0u;
+  for (const auto& c : cache)
+    if (versioned && c.limits.data_ptr() == limits.data_ptr() && c.limits.numel() == limits.numel() &&
+        c.version == ver)
+      return c.start;
+  const int64_t NB = limits.numel();
+  TORCH_CHECK_VALUE(NB >= 2 && NB <= mnistx::SUMMARY_MAX_LIMITS, "limits: needs 2 <= NB <= ",
+                    mnistx::SUMMARY_MAX_LIMITS, ", has ", NB);
+  const Tensor h = limits.cpu();
+  const double* p = h.data_ptr<double>();
+  for (int64_t i = 0; i < NB; ++i) {
+    TORCH_CHECK_VALUE(std::isfinite(p[i]), "limits: must be finite");
+    TORCH_CHECK_VALUE(i == 0 || p[i - 1] < p[i], "limits: must be strictly ascending");
+  }
+  Tensor tab = at::empty({512}, at::TensorOptions().dtype(at::kShort));
+  mnistx::summary_start_table(p, (int)NB, reinterpret_cast<uint16_t*>(tab.data_ptr()));
+  if (cache.size() >= 4) cache.erase(cache.begin());
+  cache.push_back({limits, tab.to(limits.device()), ver});
+  return cache.back().start;
+}
+
+// counts [nseg, NB + 1] / stats [nseg, 4] = min, max, sum, sum of squares of every segment
+// (offset, rows, cols, row_stride) of src against the ascending float64 limits (launchers.h).
+void summary_stats(Tensor src, Tensor segs, Tensor limits, Tensor counts, Tensor stats, Tensor scratch,
+                   double divisor) {
+  TORCH_CHECK_VALUE(src.is_cuda() && src.is_contiguous(), "src: a contiguous GPU tensor");
+  const bool bf = src.scalar_type() == at::kBFloat16;
+  TORCH_CHECK_VALUE(bf || src.scalar_type() == at::kFloat, "src: expected float32 or bfloat16, got ",
+                    src.scalar_type());
+  TORCH_CHECK_VALUE(!segs.is_cuda() && segs.scalar_type() == at::kLong && segs.dim() == 2 && segs.size(1) == 4 &&
+                        segs.is_contiguous(), "segs: CPU int64 [n,4] = (offset, rows, cols, row_stride)");
+  TORCH_CHECK_VALUE(limits.is_cuda() && limits.scalar_type() == at::kDouble && limits.dim() == 1 &&
+                        limits.is_contiguous(), "limits: a contiguous float64 [NB] GPU tensor");
+  const int64_t nseg = segs.size(0), NB = limits.numel(), total = src.numel();
+  TORCH_CHECK_VALUE(std::isfinite(divisor) && (float)divisor > 0.f && std::isfinite((float)divisor),
+                    "divisor: must be finite and > 0");
+  TORCH_CHECK_VALUE(nseg < (int64_t)1 << 20, "segs: too many segments");
+  std::vector<mnistx::SummarySeg> sv(nseg);
+  auto a = segs.accessor<int64_t, 2>();
+  for (int64_t i = 0; i < nseg; ++i) {
+    mnistx::SummarySeg& s = sv[i];
+    s.off = a[i][0];
+    s.rows = a[i][1];
+    s.cols = a[i][2];
+    s.stride = a[i][3];
+    TORCH_CHECK_VALUE(s.off >= 0 && s.rows >= 0 && s.cols >= 0 && s.stride >= 0, "segment ", i, ": negative field");
+    TORCH_CHECK_VALUE(s.cols <= s.stride, "segment ", i, ": cols ", s.cols, " > row_stride ", s.stride);
+    TORCH_CHECK_VALUE(s.rows < ((int64_t)1 << 31) && s.cols < ((int64_t)1 << 31) && s.stride < ((int64_t)1 << 31) &&
+                          s.rows * s.cols < ((int64_t)1 << 31), "segment ", i, ": 2^31 elements or more");
+    if (s.rows > 0 && s.cols > 0)
+      TORCH_CHECK_VALUE(s.off <= total && span(s.rows, s.stride, s.cols) <= total - s.off, "segment ", i,
+                        ": ends past src (", total, " elements)");
+  }
+  TORCH_CHECK_VALUE(counts.is_cuda() && counts.scalar_type() == at::kInt && counts.is_contiguous() &&
+                        counts.numel() >= nseg * (NB + 1), "counts: a contiguous int32 GPU tensor of nseg * (NB + 1)");
+  TORCH_CHECK_VALUE(stats.is_cuda() && stats.scalar_type() == at::kDouble && stats.is_contiguous() &&
+                        stats.numel() >= nseg * 4, "stats: a contiguous float64 GPU tensor of nseg * 4");
+  TORCH_CHECK_VALUE(scratch.is_cuda() && scratch.scalar_type() == at::kDouble && scratch.is_contiguous() &&
+                        scratch.numel() >= mnistx::summary_scratch_size((int)nseg),
+                    "scratch: a contiguous float64 GPU tensor of summary_scratch_size(nseg) = ",
+                    mnistx::summary_scratch_size((int)nseg));
+  TORCH_CHECK_VALUE(limits.device() == src.device() && counts.device() == src.device() &&
+                        stats.device() == src.device() && scratch.device() == src.device(),
+                    "limits / counts / stats / scratch: on the source's device");
+  const Tensor start = summary_start(limits);
+  hip_ok(mnistx::summary_stats(src.data_ptr(), bf, sv.data(), (int)nseg, P<const double>(limits),
+                               reinterpret_cast<const uint16_t*>(start.data_ptr()), (int)NB, (float)divisor,
+                               P<int>(counts), P<double>(stats), P<double>(scratch), cur_stream()),
+         "summary_stats");
+}
+
 mnistx::FinArgs prep_fin(Tensor step, Tensor stats, optional<Tensor> l2, optional<Tensor> wds, int64_t nw,
                          optional<Tensor> loss_ema, int64_t n_ema, int64_t batch, bool increment,
                          optional<Tensor> l2_ranges, optional<Tensor> ce_work, int64_t ce_nblk) {
@@ -1596,6 +1678,12 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("grad_scale"), py::arg("gnorm"),
         "gnorm[0] = sqrt(sum over all segments of (grad * grad_scale + wd * p)^2), fixed-order sums");
   m.def("grad_norm_max_blocks", []() { return (int64_t)mnistx::grad_norm_max_blocks(); });
+  m.def("summary_stats", &summary_stats, py::arg("src"), py::arg("segs"), py::arg("limits"), py::arg("counts"),
+        py::arg("stats"), py::arg("scratch"), py::arg("divisor") = 1.0,
+        "per segment (offset, rows, cols, row_stride) of src: counts[s, lower_bound(limits, v / divisor)] "
+        "(column NB: NaN, +-inf, above the last limit) and stats[s] = min, max, sum, sum of squares");
+  m.def("summary_scratch_size", [](int64_t nseg) { return (int64_t)mnistx::summary_scratch_size((int)nseg); });
+  m.def("summary_max_blocks", []() { return (int64_t)mnistx::summary_max_blocks(); });
   m.def("set_opt_fin_fused", [](int64_t on) { mnistx::set_opt_fin_fused((int)on); },
         "A/B switch of the optimizer launch running the step's finalize (MNISTX_OPT_FIN_FUSED)");
   m.def("opt_fin_fused_enabled", []() { return mnistx::opt_fin_fused_enabled() != 0; });

@@ -491,4 +491,28 @@ hipError_t finalize_step(const FinArgs& f, hipStream_t st);
 hipError_t cast_f32_bf16_padded(const float* src, bf16_t* dst, int G, int I, int J, int Ip, int Jp,
                                 hipStream_t st);
 
+// ---- summary.hip: TensorBoard summary statistics of segments of one fp32 / bf16 tensor
+// Segment s covers src[off + r * stride + c], r < rows, c < cols <= stride (the columns past cols
+// are channel padding: never read into the result), rows * cols < 2^31.  Every value is divided
+// by divisor in fp32, correctly rounded (divisor == 1: used untouched), and widened to float64.
+// counts [nseg][NB + 1]: [s][i], i < NB, the finite values whose lower_bound index in limits
+// (ascending, 2 <= NB <= SUMMARY_MAX_LIMITS) is i; [s][NB] everything else: NaN, +-inf and finite
+// values above limits[NB - 1].  stats [nseg][4]: min, max, sum, sum of squares of the values in
+// the columns < NB (none: +inf, -inf, 0, 0).  start: summary_start_table(limits) on the device.
+// scratch: summary_scratch_size(nseg) doubles, the per-(segment, block) partials of the
+// summary_max_blocks()-block reduction, combined in block order by a second launch; counts are
+// zeroed first.  Nothing read is left over from an earlier call; two calls give the same bits.
+constexpr int SUMMARY_MAX_LIMITS = 2048;
+struct SummarySeg {
+  int64_t off, rows, cols, stride;
+};
+int summary_max_blocks();
+int64_t summary_scratch_size(int nseg);
+// host: start[512] from the host copy of limits -- [e] / [256 + e]: the lower_bound index of the
+// smallest non-negative / the negative fp32 value nearest zero with biased exponent e
+void summary_start_table(const double* limits, int NB, uint16_t* start);
+hipError_t summary_stats(const void* src, bool src_bf16, const SummarySeg* segs, int nseg, const double* limits,
+                         const uint16_t* start, int NB, float divisor, int* counts, double* stats, double* scratch,
+                         hipStream_t st);
+
 }  // namespace mnistx

@@ -44,21 +44,30 @@ def scalar_value(tag: str, value: float) -> bytes:
     return proto.f_bytes(1, tag) + proto.f_float(2, float(value))
 
 
-def histogram_proto(values: np.ndarray) -> bytes:
-    v = np.asarray(values, dtype=np.float64).reshape(-1)
-    if v.size == 0:
-        v = np.zeros(1)
-    idx = np.searchsorted(BUCKET_LIMITS, v, side="left")
-    counts = np.bincount(idx, minlength=len(BUCKET_LIMITS)).astype(np.float64)
+def histogram_proto_from_stats(vmin: float, vmax: float, num: float, vsum: float, vsumsq: float,
+                               counts: np.ndarray) -> bytes:
+    """The proto from the six quantities a histogram needs; ``counts[i]`` is the number of values
+    whose ``searchsorted(BUCKET_LIMITS, v, side="left")`` is ``i`` (whoever counted them: numpy
+    below, the device in ``obs/device_summary.py``)."""
+    counts = np.asarray(counts).astype(np.float64)
     nz = np.nonzero(counts)[0]
     lo, hi = (nz[0], nz[-1]) if nz.size else (0, 0)
     # TF emits the contiguous bucket range that holds data
     limits = BUCKET_LIMITS[lo:hi + 1]
     buckets = counts[lo:hi + 1]
-    return (proto.f_double(1, float(v.min())) + proto.f_double(2, float(v.max())) +
-            proto.f_double(3, float(v.size)) + proto.f_double(4, float(v.sum())) +
-            proto.f_double(5, float((v * v).sum())) + proto.f_packed_doubles(6, limits) +
+    return (proto.f_double(1, float(vmin)) + proto.f_double(2, float(vmax)) +
+            proto.f_double(3, float(num)) + proto.f_double(4, float(vsum)) +
+            proto.f_double(5, float(vsumsq)) + proto.f_packed_doubles(6, limits) +
             proto.f_packed_doubles(7, buckets))
+
+
+def histogram_proto(values: np.ndarray) -> bytes:
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    if v.size == 0:
+        v = np.zeros(1)
+    idx = np.searchsorted(BUCKET_LIMITS, v, side="left")
+    counts = np.bincount(idx, minlength=len(BUCKET_LIMITS))
+    return histogram_proto_from_stats(v.min(), v.max(), v.size, v.sum(), (v * v).sum(), counts)
 
 
 def histogram_value(tag: str, values: np.ndarray) -> bytes:

@@ -34,7 +34,7 @@ DLMAO_TEST_SUMMARIES = "DLMAO_TEST_SUMMARIES"
 
 class Monitor:
     def __init__(self, log_dir: str, test_interval: int, max_steps: int, replica, sample: int = 64,
-                 eval_examples: Optional[int] = 10000, log=print):
+                 eval_examples: Optional[int] = 10000, log=print, device_summaries: bool = False):
         self.log_dir = log_dir
         self.test_interval, self.max_steps = test_interval, max_steps
         self.replica = replica
@@ -45,6 +45,12 @@ class Monitor:
         self._train: List[Tuple[str, Callable[[], bytes]]] = []
         self._test: List[Tuple[str, Callable[[], bytes]]] = []
         self._test_cache: Dict[str, float] = {}
+        # device_summaries: write_train computes its histograms and norms on the device
+        # (obs/device_summary.py) when the parameters live on one; _kinds: what each registered
+        # train tag is made of, for that path (tags not in it are always computed by their closure)
+        self.device_summaries = bool(device_summaries)
+        self._kinds: Dict[str, Tuple[str, str]] = {}
+        self._summarizer = None
 
     # ---- registration API (names as in monitor_cb) ------------------------
     def _fp(self):
@@ -55,10 +61,13 @@ class Monitor:
         tag = f"{layer}/{kind}"
         if kind == "weight":
             fn = lambda: self._fp().param_view(f"{layer}/weights").detach().float().cpu().numpy()  # noqa: E731
+            self._kinds[tag] = ("param_hist", f"{layer}/weights")
         elif kind == "bias":
             fn = lambda: self._fp().param_view(f"{layer}/biases").detach().float().cpu().numpy()  # noqa: E731
+            self._kinds[tag] = ("param_hist", f"{layer}/biases")
         elif kind == "activation":
             fn = lambda: self._activation(layer)  # noqa: E731
+            self._kinds[tag] = ("act_hist", layer)
         else:
             raise ValueError(kind)
         self._train.append((tag, lambda: histogram_value(tag, fn())))
@@ -66,6 +75,7 @@ class Monitor:
     def SummaryNorm2(self, kind: str, layer: str) -> None:
         tag = f"{layer}/{kind}_norm2"
         name = f"{layer}/weights" if kind == "weight" else f"{layer}/biases"
+        self._kinds[tag] = ("param_norm", name)
         self._train.append((tag, lambda: scalar_value(tag, float(self._fp().param_view(name).norm().item()))))
 
     def SummaryGradient(self, kind: str = "weight", loss=None) -> None:
@@ -74,6 +84,7 @@ class Monitor:
             if kind == "weight" and not e.name.endswith("/weights"):
                 continue
             tag = f"gradient/{e.name}"
+            self._kinds[tag] = ("grad_hist", e.name)
             self._train.append((tag, (lambda n=e.name, t=tag: histogram_value(t, self._grad(n)))))
 
     def SummaryGWRatio(self) -> None:
@@ -82,6 +93,7 @@ class Monitor:
             if not e.name.endswith("/weights"):
                 continue
             tag = f"gw_ratio/{e.name}"
+            self._kinds[tag] = ("gw_ratio", e.name)
 
             def fn(n=e.name, t=tag):
                 w = float(self._fp().param_view(n).norm().item())
@@ -132,9 +144,98 @@ class Monitor:
             a = a[..., :real]
         return a
 
+    # ---- device path (device_summaries=True and the parameters on a HIP device) ----------
+    def _on_device(self) -> bool:
+        if not self.device_summaries:
+            return False
+        fp = getattr(getattr(self.replica, "net", None), "fp", None)
+        return fp is not None and fp.params.is_cuda and fp.grads.is_cuda
+
+    def _device_activation(self, layer: str):
+        """The activation tensor as it lies on the device and its one segment: rows of the padded
+        channel count, of which the real ones count.  None: the host path takes this tag."""
+        try:
+            a = self.replica.net.layer_activation(layer, self.sample)
+        except KeyError:
+            return None
+        a = a[: self.sample].detach()
+        if not (a.is_cuda and a.dim() >= 1 and a.numel() > 0 and a.is_contiguous()
+                and a.dtype in (torch.bfloat16, torch.float32)):
+            return None
+        spec = {L.name: L for L in self.replica.spec.layers}.get(layer)
+        real = getattr(spec, "cout", None) or getattr(spec, "dout", None)
+        padded = a.shape[-1]
+        cols = real if real is not None and padded > real else padded
+        return a, (0, a.numel() // padded, cols, padded)
+
+    def _device_jobs(self):
+        """(parameter names, gradient names, {layer: (tensor, segment)}, jobs for
+        DeviceSummarizer.run): one job over the parameters, one over the gradients (divided by
+        world, as _grad does), one per activation tensor."""
+        fp = self._fp()
+        p_names: List[str] = []
+        g_names: List[str] = []
+        acts: Dict[str, tuple] = {}
+        for tag, _ in self._train:
+            kind, arg = self._kinds.get(tag, ("", ""))
+            if kind in ("param_hist", "param_norm", "gw_ratio") and arg not in p_names:
+                p_names.append(arg)
+            if kind in ("grad_hist", "gw_ratio") and arg not in g_names:
+                g_names.append(arg)
+            if kind == "act_hist" and arg not in acts:
+                t = self._device_activation(arg)
+                if t is not None:
+                    acts[arg] = t
+        flat = lambda names: [(fp.by_name[n].off, 1, fp.by_name[n].n, fp.by_name[n].n) for n in names]  # noqa: E731
+        jobs = [(fp.params, flat(p_names), 1.0), (fp.grads, flat(g_names), float(max(1, self.replica.world)))]
+        jobs += [(a, [seg], 1.0) for a, seg in acts.values()]
+        return p_names, g_names, acts, jobs
+
+    def _device_values(self) -> List[bytes]:
+        """The train summaries with every histogram and norm of a device tensor reduced there
+        and brought over in one copy.  A tensor with a NaN or an infinity (counted in the last
+        column) is redone by its closure, as is every tag that is not of a device tensor."""
+        from .device_summary import DeviceSummarizer
+        from .events import histogram_proto_from_stats
+        from ..utils import proto
+        dev = self._fp().params.device
+        if self._summarizer is None or self._summarizer.device != dev:
+            self._summarizer = DeviceSummarizer(dev)
+        nb = self._summarizer.nb
+        p_names, g_names, acts, jobs = self._device_jobs()
+        res = self._summarizer.run(jobs)
+        P = {n: (res[0][0][i], res[0][1][i]) for i, n in enumerate(p_names)}
+        G = {n: (res[1][0][i], res[1][1][i]) for i, n in enumerate(g_names)}
+        A = {n: (res[2 + i][0][0], res[2 + i][1][0]) for i, n in enumerate(acts)}
+
+        def hist(tag, cs):
+            c, s = cs
+            if c[nb] != 0:
+                return None
+            h = histogram_proto_from_stats(s[0], s[1], int(c.sum()), s[2], s[3], c[:nb])
+            return proto.f_bytes(1, tag) + proto.f_bytes(5, h)
+
+        vals = []
+        for tag, fn in self._train:
+            kind, arg = self._kinds.get(tag, ("", ""))
+            v = None
+            if kind == "param_hist":
+                v = hist(tag, P[arg])
+            elif kind == "grad_hist":
+                v = hist(tag, G[arg])
+            elif kind == "act_hist" and arg in A:
+                v = hist(tag, A[arg])
+            elif kind == "param_norm" and P[arg][0][nb] == 0:
+                v = scalar_value(tag, math.sqrt(P[arg][1][3]))
+            elif kind == "gw_ratio" and P[arg][0][nb] == 0 and G[arg][0][nb] == 0:
+                w, g = math.sqrt(P[arg][1][3]), math.sqrt(G[arg][1][3])
+                v = scalar_value(tag, g / w if w > 0 else 0.0)
+            vals.append(fn() if v is None else v)
+        return vals
+
     # ---- writers ----------------------------------------------------------------
     def write_train(self, step: int) -> None:
-        vals = [fn() for _, fn in self._train]
+        vals = self._device_values() if self._on_device() else [fn() for _, fn in self._train]
         if vals:
             self.writer.add_summary(summary(vals), step)
 

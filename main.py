@@ -91,6 +91,9 @@ flags.DEFINE_integer("max_to_keep", 5, "checkpoints to keep")
 flags.DEFINE_integer("nan_check_steps", -1, "NaN guard: read the device NaN flag every N steps, asynchronously "
                      "(a NaN at step k raises by step k + N); -1 = --log_step_count_steps (100 when that is 0)")
 flags.DEFINE_integer("eval_examples", 10000, "examples per test-summary evaluation (0: whole split)")
+flags.DEFINE_integer("monitor_device", 0, "1: the chief's train summaries (histograms, norms, gw_ratio) are reduced "
+                     "on the GPU and only bucket counts and moments are copied to the host; 0: host numpy. CPU "
+                     "executors always use the host path")
 flags.DEFINE_string("ps_backend", "", "PS-mode data plane: '' (GPU: shm for PS shards up to 1 M parameters, e.g. "
                     "LeNet-5, ipc above, e.g. the reference CNN; CPU: host) | shm (CPU parameter server "
                     "serving a shared-memory segment natively; one host) | ipc (xGMI peer copies into a GPU PS) | "
