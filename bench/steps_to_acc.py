@@ -49,6 +49,8 @@ def parse(argv=None):
     ap.add_argument("--lr_power", type=float, default=1.0, help="polynomial: the exponent")
     ap.add_argument("--label_smoothing", type=float, default=0.0,
                     help="train against (1 - eps) * onehot + eps / 10; the accuracy probe is an eval and unaffected")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="drop rate on the hidden dense layers, training only; the accuracy probe is an eval")
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
     ap.add_argument("--probe", type=int, default=10000, help="training images in the accuracy probe")
@@ -102,7 +104,8 @@ def run(args) -> dict:
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, momentum=0.9 if args.optimizer != "sgd" else 0.0,
                         nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999,
                         clip_norm=args.clip_norm, **sched)
-    opt = dataclasses.replace(opt, label_smoothing=args.label_smoothing)
+    opt = dataclasses.replace(opt, label_smoothing=args.label_smoothing, dropout=args.dropout,
+                              dropout_seed=args.seed + rank)
     init = init_params(spec, seed=args.seed)
     if args.impl == "hip":
         from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet
@@ -180,7 +183,7 @@ def run(args) -> dict:
         "config": {"model": LABEL[args.model], "global_batch": global_batch, "optimizer": args.optimizer,
                    "lr": args.lr, "lr_schedule": opt.schedule, "warmup_steps": opt.warmup_steps,
                    "lr_total_steps": opt.total_steps, "lr_end": opt.lr_end, "lr_power": opt.lr_power,
-                   "label_smoothing": opt.label_smoothing,
+                   "label_smoothing": opt.label_smoothing, "dropout": opt.dropout,
                    "eval_every": args.eval_every, "impl": args.impl, "hip_graph": graph is not None,
                    "parallelism": f"dp{world}"},
         "history": history[-20:],

@@ -448,11 +448,46 @@ void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t
          "ce_tail");
 }
 
+// The dropout arguments of a binding, validated (ValueError): the drop rate p (finite, 0 <= p < 1) as
+// the 16-bit keep threshold thr = clamp(floor((1 - p) * 65536 + 0.5), 1, 65535) and inv_keep =
+// float(65536 / thr); the seed (0 <= seed < 2^63: a Python int beyond int64 fails the conversion
+// first); the layer id, which shares a counter word with the draw group (dropout_rng.h).
+struct DropArgs {
+  uint32_t thr;
+  float inv_keep;
+};
+DropArgs dropout_rate(double p, const char* op) {
+  TORCH_CHECK_VALUE(std::isfinite(p) && p >= 0.0 && p < 1.0, op, ": dropout must be finite with 0 <= dropout < 1, got ",
+                    p);
+  const double t = std::min(std::max(std::floor((1.0 - p) * 65536.0 + 0.5), 1.0), 65535.0);
+  return DropArgs{(uint32_t)t, (float)(65536.0 / t)};
+}
+const int64_t* dropout_key(const Tensor& step, int64_t seed, int64_t layer, const char* op) {
+  TORCH_CHECK_VALUE(seed >= 0, op, ": dropout seed must be >= 0 and below 2^63, got ", seed);
+  TORCH_CHECK_VALUE(layer >= 0 && layer < mnistx::DROP_MAX_LAYER, op, ": dropout layer id must be in [0, 65536), got ",
+                    layer);
+  check(step, at::kLong, 1, "step");
+  return P<const int64_t>(step);
+}
+
 void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4, int64_t n2, Tensor w5t, Tensor b5,
               int64_t nc, Tensor labels, int64_t nb, double scale, Tensor h3, Tensor h4, Tensor logits,
               optional<Tensor> dl, optional<Tensor> dh4, optional<Tensor> dh3, optional<Tensor> dx, Tensor stats,
-              optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing) {
+              optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing, double dropout,
+              optional<Tensor> drop_step, int64_t drop_seed, int64_t drop_layer3, int64_t drop_layer4) {
   const float eps = smoothing_arg(label_smoothing, "mlp_head");
+  const DropArgs da = dropout_rate(dropout, "mlp_head");
+  mnistx::HeadDrop hd{};
+  if (dropout != 0.0) {   // 0 launches what is launched without the key
+    TORCH_CHECK_VALUE(drop_step.has_value() && drop_step->defined(), "mlp_head: dropout needs drop_step");
+    hd.step = dropout_key(*drop_step, drop_seed, drop_layer3, "mlp_head");
+    dropout_key(*drop_step, drop_seed, drop_layer4, "mlp_head");
+    hd.seed = (uint64_t)drop_seed;
+    hd.layer3 = (int)drop_layer3;
+    hd.layer4 = (int)drop_layer4;
+    hd.thr = da.thr;
+    hd.inv_keep = da.inv_keep;
+  }
   TORCH_CHECK(mnistx::mlp_head_supported(400, 120, 88, 16, (int)n1, (int)n2, (int)nc, (int)std::max<int64_t>(nb, 1)),
               "mlp_head: unsupported geometry");
   check(x, at::kBFloat16, nb * 400, "x");
@@ -492,11 +527,47 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
     db = P<float>(*dbias);
   }
   TORCH_CHECK(eps == 0.f || pdl != nullptr, "mlp_head: label_smoothing is a training quantity and needs dl");
+  TORCH_CHECK(hd.step == nullptr || pdl != nullptr, "mlp_head: dropout is a training quantity and needs dl");
   hip_ok(mnistx::mlp_head(BF(x), BF(w3t), P<const float>(b3), (int)n1, BF(w4t), P<const float>(b4), (int)n2, BF(w5t),
                           P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale, BFm(h3),
                           BFm(h4), P<float>(logits), pdl, pdh4, pdh3, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr,
-                          cur_stream(), (defer_stats && has_work) ? 1 : 0, db, eps),
+                          cur_stream(), (defer_stats && has_work) ? 1 : 0, db, eps, hd.step ? &hd : nullptr),
          "mlp_head");
+}
+
+// stand-alone dropout (dropout.hip), in place on x [nb, ld] bf16 with n real columns
+void dropout_apply(bool bwd, Tensor x, int64_t nb, int64_t n, int64_t ld, Tensor step, int64_t seed, int64_t layer,
+                   double p) {
+  const char* op = bwd ? "dropout_bwd" : "dropout_fwd";
+  const DropArgs da = dropout_rate(p, op);
+  const int64_t* st = dropout_key(step, seed, layer, op);
+  TORCH_CHECK_VALUE(nb >= 0 && nb < ((int64_t)1 << 31), op, ": nb must be in [0, 2^31), got ", nb);
+  TORCH_CHECK_VALUE(n >= 0 && n <= mnistx::DROP_MAX_N, op, ": n must be in [0, 524288], got ", n);
+  TORCH_CHECK_VALUE(ld >= n && ld % 8 == 0, op, ": ld must be a multiple of 8 and >= n, got ", ld);
+  check(x, at::kBFloat16, nb * ld, bwd ? "dy" : "x");   // whole padded rows (16-byte chunks)
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, op, ": the buffer must be 16-byte aligned");
+  TORCH_CHECK(step.device() == x.device(), op, ": step and the buffer must be on one device");
+  if (p == 0.0) return;   // rate 0 keeps everything: nothing is launched
+  hip_ok((bwd ? mnistx::dropout_bwd : mnistx::dropout_fwd)(BFm(x), nb, (int)n, (int)ld, st, (uint64_t)seed, (int)layer,
+                                                          da.thr, da.inv_keep, cur_stream()),
+         op);
+}
+void dropout_fwd(Tensor x, int64_t nb, int64_t n, int64_t ld, Tensor step, int64_t seed, int64_t layer, double p) {
+  dropout_apply(false, x, nb, n, ld, step, seed, layer, p);
+}
+void dropout_bwd(Tensor dy, int64_t nb, int64_t n, int64_t ld, Tensor step, int64_t seed, int64_t layer, double p) {
+  dropout_apply(true, dy, nb, n, ld, step, seed, layer, p);
+}
+// the keep bits of (seed, step, layer) as uint8 [nb, n]
+void dropout_mask(Tensor out, int64_t nb, int64_t n, Tensor step, int64_t seed, int64_t layer, double p) {
+  const DropArgs da = dropout_rate(p, "dropout_mask");
+  const int64_t* st = dropout_key(step, seed, layer, "dropout_mask");
+  TORCH_CHECK_VALUE(nb >= 0 && nb < ((int64_t)1 << 31), "dropout_mask: nb must be in [0, 2^31), got ", nb);
+  TORCH_CHECK_VALUE(n >= 0 && n <= mnistx::DROP_MAX_N, "dropout_mask: n must be in [0, 524288], got ", n);
+  check(out, at::kByte, nb * n, "out");
+  TORCH_CHECK(step.device() == out.device(), "dropout_mask: step and out must be on one device");
+  hip_ok(mnistx::dropout_mask(P<uint8_t>(out), nb, (int)n, st, (uint64_t)seed, (int)layer, da.thr, cur_stream()),
+         "dropout_mask");
 }
 
 mnistx::RedSpec red_spec(Tensor slab, int64_t splits, int64_t M, int64_t N, int64_t G, int64_t Ipad, int64_t I,
@@ -1648,7 +1719,14 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("scale"), py::arg("h3"), py::arg("h4"), py::arg("logits"), py::arg("dl") = py::none(),
         py::arg("dh4") = py::none(), py::arg("dh3") = py::none(), py::arg("dx") = py::none(), py::arg("stats"),
         py::arg("work"), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
-        py::arg("label_smoothing") = 0.0);
+        py::arg("label_smoothing") = 0.0, py::arg("dropout") = 0.0, py::arg("drop_step") = py::none(),
+        py::arg("drop_seed") = 0, py::arg("drop_layer3") = 0, py::arg("drop_layer4") = 0);
+  m.def("dropout_fwd", &dropout_fwd, py::arg("x"), py::arg("nb"), py::arg("n"), py::arg("ld"), py::arg("step"),
+        py::arg("seed"), py::arg("layer"), py::arg("p"));
+  m.def("dropout_bwd", &dropout_bwd, py::arg("dy"), py::arg("nb"), py::arg("n"), py::arg("ld"), py::arg("step"),
+        py::arg("seed"), py::arg("layer"), py::arg("p"));
+  m.def("dropout_mask", &dropout_mask, py::arg("out"), py::arg("nb"), py::arg("n"), py::arg("step"), py::arg("seed"),
+        py::arg("layer"), py::arg("p"));
   m.def("fused_optimizer", &fused_optimizer, py::arg("params"), py::arg("grads"), py::arg("mom"), py::arg("ema"),
         py::arg("bf"), py::arg("segs"), py::arg("step"), py::arg("lr0"), py::arg("decay_rate"),
         py::arg("decay_steps"), py::arg("momentum"), py::arg("nesterov"), py::arg("use_momentum"),

@@ -298,13 +298,25 @@ int softmax_ce_dbias_blocks(int B, int ldl);
 // Fused LeNet-5 dense head (mlp_head.hip): fc3/fc4/fc5 + softmax-CE (+ with dl:
 // the data-gradient chain dlogits -> dh4 -> dh3 -> dx).  Writes h3, h4, logits
 // always; dl, dh4, dh3, dx when dl != nullptr.  Same work-buffer contract as softmax_ce.
+// dropout on h3 / h4 inside mlp_head (dropout_rng.h; the gradient form only): the device-side global
+// step, the seed, the two layer ids, the 16-bit keep threshold and 65536 / thr.  nullptr: the plain
+// (or smoothed) instantiation with its own arguments.
+// (the layer id shares a counter word with the draw group f >> 3: 16 bits each)
+constexpr int64_t DROP_MAX_LAYER = 65536, DROP_MAX_N = 524288;
+struct HeadDrop {
+  const int64_t* step;
+  uint64_t seed;
+  int layer3, layer4;
+  uint32_t thr;
+  float inv_keep;
+};
 bool mlp_head_supported(int d0, int ld1, int ld2, int ld3, int n1, int n2, int nc, int B);
 // w3t / w4t / w5t: zero-padded W^T copies [128][416], [96][128], [16][96].
 hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t, const float* b4,
                     int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
                     bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
                     float* stats, float* work, hipStream_t st, int defer_stats = 0, float* dbias = nullptr,
-                    float label_smoothing = 0.f);
+                    float label_smoothing = 0.f, const HeadDrop* drop = nullptr);
 // blocks of one mlp_head launch (its per-block CE partials when defer_stats is set)
 int mlp_head_blocks(int nb);
 // the reference CNN's softmax_linear (192 -> nc <= 16) + softmax CE + its data gradient (masked by
@@ -326,6 +338,23 @@ hipError_t mlp_head_smooth(const bf16_t* x, const bf16_t* w3t, const float* b3, 
                            int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
                            bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
                            float* dbias, float label_smoothing);
+// the dropped instantiations (mlp_head_drop.hip), with label smoothing or without
+hipError_t mlp_head_drop(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
+                         const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
+                         int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
+                         bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
+                         float* dbias, float label_smoothing, const HeadDrop& drop);
+// Stand-alone dropout (dropout.hip) on a [nb, ld] bf16 buffer with n <= ld real columns, in place:
+// x = keep ? bf16(x * inv_keep) : +0, the keep bits of (seed, *step, layer) from dropout_rng.h.
+// Forward (on the activation) and backward (on the gradient: the bits are recomputed) are the same
+// walk; columns >= n and rows >= nb are not written.  ld % 8 == 0, x 16-byte aligned.
+hipError_t dropout_fwd(bf16_t* x, int64_t nb, int n, int ld, const int64_t* step, uint64_t seed, int layer,
+                       uint32_t thr, float inv_keep, hipStream_t st);
+hipError_t dropout_bwd(bf16_t* dy, int64_t nb, int n, int ld, const int64_t* step, uint64_t seed, int layer,
+                       uint32_t thr, float inv_keep, hipStream_t st);
+// the keep bits themselves, uint8 [nb, n] (what lr_at_steps is to the schedule: for the tests)
+hipError_t dropout_mask(uint8_t* out, int64_t nb, int n, const int64_t* step, uint64_t seed, int layer, uint32_t thr,
+                        hipStream_t st);
 // NOTE: many splits over a small output are pre-summed IN PLACE (the slab is scratch).
 hipError_t splitk_reduce(float* slab, int splits, int M, int N, int G, int Ipad, int I, int J,
                          int bias_row, float* wdst, float* bdst, float scale, hipStream_t st);

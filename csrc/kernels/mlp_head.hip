@@ -33,9 +33,11 @@
 //  vs ~130 us for the 8 layered launches it replaces.
 #include "ce_stats.h"
 #include "common.h"
+#include "dropout_rng.h"
 #include "launchers.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -177,11 +179,50 @@ DEV float smooth_loss(const float (&lg)[8], float mx, float se, float ll, int h,
   return fmaf(-off, sd, fmaf(-on, ll - mx, __logf(se)));
 }
 
+// The trailing argument pack of mlp_head_k: eps (SMOOTH) first, then the dropout arguments.  DROP is
+// read off the pack's types instead of being one more template argument, so the plain and the
+// smoothed instantiation keep the names (and the code objects) they had before dropout existed.
+template <typename... A>
+constexpr bool pack_has_drop = (std::is_same_v<A, HeadDrop> || ...);
+DEV float pack_eps(float e) { return e; }
+DEV float pack_eps(float e, const HeadDrop&) { return e; }
+DEV const HeadDrop& pack_drop(const HeadDrop& d) { return d; }
+DEV const HeadDrop& pack_drop(float, const HeadDrop& d) { return d; }
+
+// The draws of features 8g + 4h .. + 3 (registers 4q .. 4q + 3 of a tile, draw group g = 4 tile + q)
+// of batch row m: words 2h and 2h + 1 of group g's Philox call.  The two half-row lanes need every
+// group; lane half h makes the call of group (g & ~1) + h alone and the two trade the words the other
+// needs (__shfl_xor 32): 14 calls per lane for h3 and h4 instead of 28 (measured 36.2 - 37.1 us
+// against 38.3 - 38.9 us with both lanes making every call, B = 65536,
+// profiles/r7/dropout/README.md).  Both groups of a pair ask for the same call and the same two
+// exchanges; it is written per group so that the packing loops keep their shape, and the compiler
+// merges the two (228 v_mul_hi_u32 in the disassembly, 14 calls' worth; both lanes calling: 424).
+DEV void drop_words(const DropKey& k, uint32_t m, uint32_t g, int h, uint32_t& w0, uint32_t& w1) {
+  const u32x4 c = drop_draws(k, m, (g & ~1u) + h);
+  const uint32_t r0 = __shfl_xor(h ? c[0] : c[2], 32, 64), r1 = __shfl_xor(h ? c[1] : c[3], 32, 64);
+  // an even group was drawn by half 0, an odd one by half 1
+  w0 = (g & 1) ? (h ? c[2] : r0) : (h ? r0 : c[0]);
+  w1 = (g & 1) ? (h ? c[3] : r1) : (h ? r1 : c[1]);
+}
+// bias + ReLU + dropout of those 4 features -> two packed bf16 words.  A dropped unit is +0 by a
+// select (never NaN * 0); a kept one is scaled before the one bf16 rounding.
+DEV void drop_pack(const DropKey& k, float inv_keep, uint32_t m, uint32_t g, int h, const float (&v)[4], uint32_t& p0,
+                   uint32_t& p1) {
+  uint32_t w0, w1;
+  drop_words(k, m, g, h, w0, w1);
+  p0 = pack2(keep_lo(w0, k.thr) ? v[0] * inv_keep : 0.f, keep_hi(w0, k.thr) ? v[1] * inv_keep : 0.f);
+  p1 = pack2(keep_lo(w1, k.thr) ? v[2] * inv_keep : 0.f, keep_hi(w1, k.thr) ? v[3] * inv_keep : 0.f);
+}
+
 // NW waves per block, TPW 32-row tiles per wave.  The launch uses TPW = 1 (every wave's
 // load / compute / store phases in lockstep); TPW = 2 with 4 waves (the next tile's X
 // loads under the current tile's backward chain) measured slower (0.540 vs 0.53 ms/step,
 // profiles/r3/lenet/knobs/).
-// SMOOTH: label smoothing (ce_stats.h), eps as the one member of the trailing argument pack.
+// SMOOTH: label smoothing (ce_stats.h), eps as the first member of the trailing argument pack.
+// DROP (a HeadDrop closes the pack; gradient form only): dropout on h3 and h4 (dropout_rng.h).  The
+// masks are drawn where the activations are packed; h3 / h4 are stored dropped and scaled, so the
+// weight and bias gradients need nothing; the backward reads the bit off the packed activation
+// (h' > 0 exactly for a kept unit that passed the ReLU; a unit that is 0 has gradient 0 either way).
 template <bool GRADS, int NW = NWAVE, int TPW = 1, bool SMOOTH = false, typename... EPS>
 __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W3t,
                                                   const float* __restrict__ b3, int n1, const bf16_t* __restrict__ W4t,
@@ -194,7 +235,9 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
                                                   bf16_t* __restrict__ dx, float* __restrict__ stats,
                                                   float* __restrict__ work, int defer_stats,
                                                   float* __restrict__ dbias, EPS... eps) {
-  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
+  constexpr bool DROP = pack_has_drop<EPS...>;
+  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0) + (DROP ? 1 : 0), "the pack is [eps] [HeadDrop]");
+  static_assert(GRADS || !DROP, "dropout is a training quantity: the gradient form only");
   __shared__ __attribute__((aligned(16))) bf16_t i3[R3 * S3];
   __shared__ __attribute__((aligned(16))) bf16_t i4[R4 * S4];
   __shared__ __attribute__((aligned(16))) bf16_t i5[R5 * S5];
@@ -282,8 +325,16 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
       for (int q = 0; q < 4; ++q) {
         const int n = 32 * t + 8 * q + 4 * h;
         const f32x4 bb = *(const f32x4*)(bias3 + n);
+        if constexpr (DROP) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
+          const HeadDrop& dr = pack_drop(eps...);
+          const float v[4] = {fmaxf(a1[t][4 * q] + bb[0], 0.f), fmaxf(a1[t][4 * q + 1] + bb[1], 0.f),
+                              fmaxf(a1[t][4 * q + 2] + bb[2], 0.f), fmaxf(a1[t][4 * q + 3] + bb[3], 0.f)};
+          drop_pack(drop_key(dr.step, dr.seed, dr.layer3, dr.thr), dr.inv_keep, (uint32_t)m, 4 * t + q, h, v,
+                    h3p[t][2 * q], h3p[t][2 * q + 1]);
+        } else {
         h3p[t][2 * q] = pack2(fmaxf(a1[t][4 * q] + bb[0], 0.f), fmaxf(a1[t][4 * q + 1] + bb[1], 0.f));
         h3p[t][2 * q + 1] = pack2(fmaxf(a1[t][4 * q + 2] + bb[2], 0.f), fmaxf(a1[t][4 * q + 3] + bb[3], 0.f));
+        }
       }
 #pragma unroll
       for (int t = 0; t < T1; ++t) store_tile(stg, h3p[t], h3, LD1, m0, nb, 32 * t, LD1 - 32 * t, lane);
@@ -309,8 +360,16 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
       for (int q = 0; q < 4; ++q) {
         const int n = 32 * u + 8 * q + 4 * h;
         const f32x4 bb = *(const f32x4*)(bias4 + n);
+        if constexpr (DROP) {
+          const HeadDrop& dr = pack_drop(eps...);
+          const float v[4] = {fmaxf(a2[u][4 * q] + bb[0], 0.f), fmaxf(a2[u][4 * q + 1] + bb[1], 0.f),
+                              fmaxf(a2[u][4 * q + 2] + bb[2], 0.f), fmaxf(a2[u][4 * q + 3] + bb[3], 0.f)};
+          drop_pack(drop_key(dr.step, dr.seed, dr.layer4, dr.thr), dr.inv_keep, (uint32_t)m, 4 * u + q, h, v,
+                    h4p[u][2 * q], h4p[u][2 * q + 1]);
+        } else {
         h4p[u][2 * q] = pack2(fmaxf(a2[u][4 * q] + bb[0], 0.f), fmaxf(a2[u][4 * q + 1] + bb[1], 0.f));
         h4p[u][2 * q + 1] = pack2(fmaxf(a2[u][4 * q + 2] + bb[2], 0.f), fmaxf(a2[u][4 * q + 3] + bb[3], 0.f));
+        }
       }
 #pragma unroll
       for (int u = 0; u < T2; ++u) store_tile(stg, h4p[u], h4, LD2, m0, nb, 32 * u, LD2 - 32 * u, lane);
@@ -353,7 +412,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
     for (int i = 0; i < 8; ++i) ll = ((i & 3) + 8 * (i >> 2) + 4 * h == lab) ? lg[i] : ll;
     ll += __shfl_xor(ll, 32, 64);
     if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
-      const float lo = smooth_loss(lg, mx, se, ll, h, nc, smooth_eps(eps...));   // by both half-rows
+      const float lo = smooth_loss(lg, mx, se, ll, h, nc, pack_eps(eps...));   // by both half-rows
       if (valid && h == 0) {
         loss += lo;
         corr += (ll >= mx) ? 1.f : 0.f;
@@ -375,7 +434,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
         for (int k = 0; k < 2; ++k) {
           const int i = 2 * w + k, cls = (i & 3) + 8 * (i >> 2) + 4 * h;
           if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
-            const float off = smooth_eps(eps...) / (float)nc, on = 1.f - smooth_eps(eps...);
+            const float off = pack_eps(eps...) / (float)nc, on = 1.f - pack_eps(eps...);
             g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? on + off : off)) * scale : 0.f;
           } else {
             g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? 1.f : 0.f)) * scale : 0.f;
@@ -402,6 +461,11 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
         const f32x16 acc = mfma32(join(lo, hi), db, f32x16{});
 #pragma unroll
         for (int w = 0; w < 8; ++w) {
+          if constexpr (DROP) {   // h4' > 0: kept and past the ReLU
+            const float ik = pack_drop(eps...).inv_keep;
+            d4p[u][w] = pack2(pos_lo(h4p[u][w]) ? acc[2 * w] * ik : 0.f, pos_hi(h4p[u][w]) ? acc[2 * w + 1] * ik : 0.f);
+            continue;
+          }
           const float v0 = pos_lo(h4p[u][w]) ? acc[2 * w] : 0.f;
           const float v1 = pos_hi(h4p[u][w]) ? acc[2 * w + 1] : 0.f;
           d4p[u][w] = pack2(v0, v1);
@@ -431,6 +495,11 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
       for (int t = 0; t < T1; ++t) {
 #pragma unroll
         for (int w = 0; w < 8; ++w) {
+          if constexpr (DROP) {
+            const float ik = pack_drop(eps...).inv_keep;
+            d3p[t][w] = pack2(pos_lo(h3p[t][w]) ? d3[t][2 * w] * ik : 0.f, pos_hi(h3p[t][w]) ? d3[t][2 * w + 1] * ik : 0.f);
+            continue;
+          }
           const float v0 = pos_lo(h3p[t][w]) ? d3[t][2 * w] : 0.f;
           const float v1 = pos_hi(h3p[t][w]) ? d3[t][2 * w + 1] : 0.f;
           d3p[t][w] = pack2(v0, v1);
@@ -678,6 +747,27 @@ hipError_t mlp_head_smooth(const bf16_t* x, const bf16_t* w3t, const float* b3, 
                      label_smoothing);
   return hipGetLastError();
 }
+#elif defined(MNISTX_HEAD_DROP_TU)
+// mlp_head_drop.hip: the dropped instantiations (with and without label smoothing), a translation
+// unit of their own for the same reason.  GRADS = false has no dropped form.
+hipError_t mlp_head_drop(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
+                         const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
+                         int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
+                         bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
+                         float* dbias, float label_smoothing, const HeadDrop& drop) {
+  if (nb <= 0) return hipSuccess;
+  if (!dl || !drop.step) return hipErrorInvalidValue;
+  const dim3 grid((nb + ROWS - 1) / ROWS);
+  if (label_smoothing != 0.f)
+    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float, HeadDrop>), grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t,
+                       b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work,
+                       defer_stats, dbias, label_smoothing, drop);
+  else
+    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, false, HeadDrop>), grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4,
+                       n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work, defer_stats,
+                       dbias, drop);
+  return hipGetLastError();
+}
 #else
 // waves per block (32 rows each): 2, or more when the block count would exceed the CE partial
 // slots; MNISTX_CE_TAIL_NW overrides (1, 2 or 4).  At B = 16384 2 waves (256 blocks) measured
@@ -730,7 +820,11 @@ bool mlp_head_supported(int d0, int ld1, int ld2, int ld3, int n1, int n2, int n
 hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t, const float* b4,
                     int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
                     bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
-                    float* stats, float* work, hipStream_t st, int defer_stats, float* dbias, float label_smoothing) {
+                    float* stats, float* work, hipStream_t st, int defer_stats, float* dbias, float label_smoothing,
+                    const HeadDrop* drop) {
+  if (drop)
+    return mlp_head_drop(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx,
+                         stats, work, st, defer_stats, dbias, label_smoothing, *drop);
   if (label_smoothing != 0.f)
     return mlp_head_smooth(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3,
                            dx, stats, work, st, defer_stats, dbias, label_smoothing);

@@ -73,8 +73,11 @@ def _pool_same(x: torch.Tensor, k: int, s: int, padding: str) -> torch.Tensor:
 
 
 def forward(spec: ModelSpec, params: Dict[str, torch.Tensor], x: torch.Tensor,
-            keep_activations: bool = False) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
-    """x: [B, H*W*C] or [B, H, W, C] (NHWC).  Returns (logits [B, classes], acts)."""
+            keep_activations: bool = False,
+            dropout: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """x: [B, H*W*C] or [B, H, W, C] (NHWC).  Returns (logits [B, classes], acts).
+    ``dropout``: {Dense layer name: multiplier [B, dout]} applied to that layer's output after its
+    ReLU (inverted dropout: 1 / keep probability where kept, 0 where dropped; ops/dropout.py)."""
     h, w = spec.input_hw
     x = x.reshape(-1, h, w, spec.in_channels).permute(0, 3, 1, 2)  # NCHW for torch ops
     acts: Dict[str, torch.Tensor] = {}
@@ -99,6 +102,8 @@ def forward(spec: ModelSpec, params: Dict[str, torch.Tensor], x: torch.Tensor,
             x = x @ params[f"{L.name}/weights"] + params[f"{L.name}/biases"]
             if L.relu:
                 x = F.relu(x)
+            if dropout is not None and L.name in dropout:
+                x = x * dropout[L.name].to(x.dtype)
         if keep_activations:
             acts[L.name] = x.permute(0, 2, 3, 1) if x.dim() == 4 else x
     return x, acts

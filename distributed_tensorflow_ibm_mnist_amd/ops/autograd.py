@@ -185,6 +185,31 @@ class SoftmaxCrossEntropyFn(torch.autograd.Function):
         return dl.float() * dloss, None, None, None
 
 
+class DropoutFn(torch.autograd.Function):
+    """Inverted dropout over the trailing dimension (padded to a multiple of 8 columns), masks from
+    the counter-based generator at the value ``step`` holds when the forward runs (csrc/kernels/
+    dropout.hip).  No mask is saved: the backward recomputes the bits from a copy of the step."""
+
+    @staticmethod
+    def forward(ctx, x, step, seed: int, layer: int, p: float):
+        n = x.shape[-1]
+        if n % 8:
+            raise ValueError(f"dropout needs a trailing dimension padded to a multiple of 8, got {n}")
+        y = x.to(torch.bfloat16).contiguous().clone()
+        Fk.dropout(y.view(-1, n), step, seed, layer, p)
+        ctx.save_for_backward(step.clone())     # the step may move on before the backward runs
+        ctx.meta = (seed, layer, p, n)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (step,) = ctx.saved_tensors
+        seed, layer, p, n = ctx.meta
+        g = dy.to(torch.bfloat16).contiguous().clone()
+        Fk.dropout(g.view(-1, n), step, seed, layer, p, backward=True)
+        return g, None, None, None, None
+
+
 def conv2d(x, w, b=None, padding: str = "SAME", relu: bool = True, cout_pad: Optional[int] = None):
     return Conv2dFn.apply(x, w, b, padding, relu, cout_pad or Fk.pad8(w.shape[-1]))
 
@@ -209,3 +234,8 @@ def lrn(x, r: int = 4, bias: float = 1.0, alpha: float = 0.001 / 9.0, beta: floa
 def softmax_cross_entropy(logits, labels, n_classes: int, label_smoothing: float = 0.0):
     """Returns (mean loss, stats f32[8]: [sum CE, #correct, nonfinite flag, ...])."""
     return SoftmaxCrossEntropyFn.apply(logits, labels, n_classes, label_smoothing)
+
+
+def dropout(x, step, seed: int, layer: int, p: float):
+    """Inverted dropout of ``x`` ([..., n] with n % 8 == 0) at the device step ``step`` (int64[1])."""
+    return DropoutFn.apply(x, step, seed, layer, p)

@@ -293,3 +293,23 @@ def softmax_probs(logits: torch.Tensor, n_classes: int, out: Optional[torch.Tens
         out = torch.empty(B, n_classes, dtype=torch.float32, device=logits.device)
     kernels().softmax_ce(logits, ld, None, B, n_classes, 1.0, None, ld, None, out)
     return out
+
+
+def dropout(x: torch.Tensor, step: torch.Tensor, seed: int, layer: int, p: float, n: Optional[int] = None,
+            backward: bool = False) -> torch.Tensor:
+    """Inverted dropout IN PLACE on a bf16 [rows, ld] buffer (``n`` real columns, default ld; ld a
+    multiple of 8): x = keep ? bf16(x / keep_prob) : +0, the keep bits a pure function of
+    (seed, step[0], layer, row, feature) (``ops/dropout.py`` is the host reference).  ``step`` is a
+    device int64[1] read by the kernel, so the call is hipGraph-safe.  ``backward``: the same walk
+    over a gradient buffer (the bits are recomputed).  Returns ``x``."""
+    rows, ld = x.shape
+    kern = kernels().dropout_bwd if backward else kernels().dropout_fwd
+    kern(x, rows, ld if n is None else n, ld, step, seed, layer, p)
+    return x
+
+
+def dropout_mask(step: torch.Tensor, seed: int, layer: int, rows: int, n: int, p: float) -> torch.Tensor:
+    """The keep bits the dropout kernels apply at (seed, step[0], layer): uint8 [rows, n]."""
+    out = torch.empty(rows, n, dtype=torch.uint8, device=step.device)
+    kernels().dropout_mask(out, rows, n, step, seed, layer, p)
+    return out

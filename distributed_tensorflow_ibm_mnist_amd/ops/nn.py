@@ -84,6 +84,28 @@ class SoftmaxCrossEntropy(nn.Module):
         return loss
 
 
+class Dropout(nn.Module):
+    """Inverted dropout with drop rate ``p`` over the stand-alone HIP kernels.  The masks are a pure
+    function of (seed, step, layer, row, feature) (``ops/dropout.py``), rows being those of the
+    input flattened to [-1, features]; the module keeps its own device step, incremented once per
+    training forward, and is the identity in ``.eval()``."""
+
+    def __init__(self, p: float = 0.5, seed: int = 0, layer: int = 0):
+        super().__init__()
+        from .dropout import check_rate, check_seed
+        self.p, self.seed, self.layer = check_rate(p, "p"), check_seed(seed, "seed"), int(layer)
+        if not 0 <= self.layer < 65536:
+            raise ValueError(f"layer must be in [0, 65536), got {layer}")
+        self.register_buffer("step", torch.zeros(1, dtype=torch.int64))
+
+    def forward(self, x):
+        if not self.training or self.p == 0:
+            return x
+        y = A.dropout(x, self.step, self.seed, self.layer, self.p)
+        self.step += 1          # on the device, after the launch that read it: no host sync
+        return y
+
+
 class HipModel(nn.Sequential):
     """A ModelSpec as modules; input [B, H, W, C] (any float dtype), output fp32
     logits [B, max(16, pad8(classes))] (columns >= num_classes are 0)."""

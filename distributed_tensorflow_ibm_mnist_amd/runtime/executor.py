@@ -529,6 +529,13 @@ class HipNet:
                                  and all(l.Dp % 8 == 0 and l.Np % 8 == 0 for l in self.layers[self.head:]))
         self._group_S: Optional[list] = None
         self._head_grads = False                   # loss_and_grad already produced the head's dgrads
+        # dropout (ops/dropout.py): the layers whose output is dropped -- every hidden ReLU Dense --
+        # and whether the current pass is a training one (set by forward; eval passes read x0)
+        self.drop_layers = {k for k, l in enumerate(self.layers)
+                            if isinstance(l, DenseLayer) and l.spec.relu and not l.last} if self.opt.dropout > 0 else set()
+        if any(self.layers[k].idx >= 65536 for k in self.drop_layers):
+            raise ValueError("dropout: a dropped layer's index in ModelSpec.layers must be below 65536")
+        self._drop_pass = False
         # reference CNN: norm1's backward runs in conv1's weight-gradient staging (reads
         # dL/d norm1 + pool1, no pool-level gradient in HBM, no lrn_bwd launch)
         self.fold_lrn = False
@@ -647,6 +654,11 @@ class HipNet:
         defer = grads and stats is self.stats and self.ce_work is not None
         # label smoothing shapes the training loss alone: the eval form keeps the hard labels
         eps = self.opt.label_smoothing if grads else 0.0
+        # and so does dropout: the dropped instantiation draws the masks of h3 / h4 in registers
+        drop = {}
+        if grads and self._drop_pass and self.head_kind == "mlp":
+            drop = dict(dropout=self.opt.dropout, drop_step=self.fp.step, drop_seed=self.opt.dropout_seed,
+                        drop_layer3=self.layers[i].idx, drop_layer4=self.layers[i + 1].idx)
         if self.head_kind == "tail":
             l5 = self.layers[i]
             K = kernels()
@@ -668,7 +680,7 @@ class HipNet:
                            dl=self.dlogits if grads else None, dh4=self.dbuf[i + 2] if grads else None,
                            dh3=self.dbuf[i + 1] if grads else None, dx=self.dbuf[i] if grads else None,
                            stats=stats, work=self.ce_work, defer_stats=defer,
-                           dbias=self.ce_dbias if grads else None, label_smoothing=eps)
+                           dbias=self.ce_dbias if grads else None, label_smoothing=eps, **drop)
         if grads:
             l5.ce_bias = (self.ce_dbias, kernels().mlp_head_blocks(nb))
         if defer:
@@ -718,7 +730,9 @@ class HipNet:
         ``from_x0`` forces the bf16 ``x0`` buffer (eval / inference / tests).
         ``defer_head``: a fused dense head is left to ``loss_and_grad`` (which then
         runs head forward + softmax-CE + head data gradients as one kernel), so the
-        logits are only valid after it."""
+        logits are only valid after it.
+        With ``opt.dropout`` > 0 a training forward (not ``from_x0``) drops the hidden ReLU dense
+        layers' outputs, and the ``loss_and_grad`` / ``backward`` that follow it their gradients."""
         nb = self.B if nb is None else nb
         first = self.layers[0]
         if isinstance(first, ConvPoolLayer):
@@ -728,10 +742,18 @@ class HipNet:
         if self.band_fwd and stop >= 2:
             self._band_forward(nb)
             start = 2
-        for lay in self.layers[start:stop]:
+        self._drop_pass = bool(self.drop_layers) and not from_x0
+        for k, lay in enumerate(self.layers[start:stop], start):
             lay.fwd(nb)
+            if self._drop_pass and k in self.drop_layers:
+                self._dropout(kernels().dropout_fwd, lay, lay.out, nb)
         self._head_pending = nb if stop < len(self.layers) else None
         return self.logits
+
+    def _dropout(self, kern, lay: DenseLayer, buf: torch.Tensor, nb: int) -> None:
+        """The stand-alone dropout kernels (dropout.hip) on a dropped layer's output or on the
+        gradient with respect to it, in place; the masks of (dropout_seed, fp.step, lay.idx)."""
+        kern(buf, nb, lay.spec.dout, lay.Np, self.fp.step, self.opt.dropout_seed, lay.idx, self.opt.dropout)
 
     def _band_forward(self, nb: int) -> None:
         """conv1 -> pool1 -> conv2 -> pool2 in one launch; writes both layers' pooled
@@ -808,6 +830,11 @@ class HipNet:
         for i in range(len(self.layers) - 1, -1, -1):
             lay = self.layers[i]
             dx = self.dbuf[i]
+            # dropout backward on dL/d(this layer's output), complete once the layer above (or
+            # ce_tail) has written it: before this layer's own weight and data gradients.  The
+            # fused head applied it to its own layers already.
+            if self._drop_pass and i in self.drop_layers and not (self._head_grads and i >= self.head):
+                self._dropout(kernels().dropout_bwd, lay, dy, nb)
             if i == 1 and self.fused_bwd:
                 self._fused_conv_backward(nb, dy, pending)
                 for li in (self.layers[1].idx, self.layers[0].idx):

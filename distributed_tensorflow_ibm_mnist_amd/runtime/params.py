@@ -72,8 +72,16 @@ class OptConfig:
     # softmax-CE kernels' smoothed instantiations); eval paths keep the hard labels.  Not an
     # optimizer quantity, but OptConfig is the nets' one training-config channel.
     label_smoothing: float = 0.0
+    # inverted dropout (drop rate, as torch.nn.Dropout) on the output of every hidden ReLU Dense
+    # layer, training paths only; the masks are a pure function of (dropout_seed, global step,
+    # layer, row, feature) (ops/dropout.py), so there is no state.  0: nothing extra is launched.
+    dropout: float = 0.0
+    dropout_seed: int = 0
 
     def __post_init__(self):
+        from ..ops.dropout import check_rate, check_seed
+        self.dropout = check_rate(self.dropout, "dropout")
+        self.dropout_seed = check_seed(self.dropout_seed, "dropout_seed")
         try:
             if isinstance(self.label_smoothing, bool):
                 raise ValueError
@@ -123,9 +131,9 @@ class OptConfig:
 
     @staticmethod
     def from_spec(spec, decay_steps: int, decay_rate: float, ema: float = 0.9999,
-                  label_smoothing: float = 0.0) -> "OptConfig":
-        """From a parameter-manager ``OptimizerSpec`` (which does not carry ``label_smoothing``:
-        the caller passes ``getLabelSmoothing()``)."""
+                  label_smoothing: float = 0.0, dropout: float = 0.0, dropout_seed: int = 0) -> "OptConfig":
+        """From a parameter-manager ``OptimizerSpec`` (which does not carry ``label_smoothing`` or
+        the dropout keys: the caller passes ``getLabelSmoothing()``, ``getDropout()`` and the seed)."""
         lr = spec.learning_rate
         adaptive = spec.name in ADAPTIVE_RULES + LAYERWISE_RULES
         return OptConfig(lr0=float(lr), decay_rate=float(decay_rate), decay_steps=int(decay_steps),
@@ -141,7 +149,7 @@ class OptConfig:
                          warmup_steps=getattr(spec, "warmup_steps", 0),
                          total_steps=getattr(spec, "lr_total_steps", 0),
                          lr_end=getattr(spec, "lr_end", 0.0), lr_power=getattr(spec, "lr_power", 1.0),
-                         label_smoothing=label_smoothing)
+                         label_smoothing=label_smoothing, dropout=dropout, dropout_seed=dropout_seed)
 
     @property
     def scheduled(self) -> bool:

@@ -168,11 +168,23 @@ class TorchNet:
         leaf = self.fp.params.detach().requires_grad_(grad)
         self._leaf = leaf
         x = self.x0[:nb].float() if not self.autocast else self.x0[:nb]
+        # dropout on the training forward alone (grad=True; eval_batch / probs pass grad=False): the
+        # host reference's masks at the current global step, bit for bit the HIP executor's
+        drop = self.dropout_multipliers(nb) if (grad and self.opt.dropout > 0) else None
         with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.autocast):
-            logits, acts = torch_ref.forward(self.spec, self._params(leaf), x, keep_activations=self.keep_activations)
+            logits, acts = torch_ref.forward(self.spec, self._params(leaf), x, keep_activations=self.keep_activations,
+                                             dropout=drop)
         self._acts = acts
         self._logits = logits.float()
         return self._logits
+
+    def dropout_multipliers(self, nb: int, step: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """{layer name: multiplier [nb, dout]} of the dropped layers at ``step`` (default: now)."""
+        from ..ops import dropout as D
+        t = int(self.fp.step.item()) if step is None else int(step)
+        return {name: torch.from_numpy(D.multiplier(self.opt.dropout_seed, t, idx, nb, self.spec.layers[idx].dout,
+                                                    self.opt.dropout)).to(self.device)
+                for name, idx in D.dropout_layers(self.spec).items()}
 
     def loss_and_grad(self, nb: Optional[int] = None, scale: Optional[float] = None) -> None:
         nb = self.B if nb is None else nb

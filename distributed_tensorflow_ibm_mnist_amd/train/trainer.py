@@ -78,6 +78,7 @@ def train(FLAGS, log=print) -> Dict[str, float]:
     pm.check_ps_optimizer(FLAGS.job_name, log)    # before setup_distribute opens any socket
     pm.check_ps_clip_norm(FLAGS.job_name, log)
     pm.check_ps_lr_schedule(FLAGS.job_name, log)
+    pm.check_ps_dropout(FLAGS.job_name, log)
     max_steps = pm.getMaxSteps()                  # main.py:38-40
     test_interval = pm.getTestInterval()
     batch_size = pm.getTrainBatchSize()
@@ -104,7 +105,10 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
     spec = models.get_model(FLAGS.model, FLAGS.in_channels)
     lr0 = pm.getBaseLearningRate()
     opt = OptConfig.from_spec(pm.getOptimizer(lr0), decay_steps_for(batch_size), pm.getLearningRateDecay(),
-                              MOVING_AVERAGE_DECAY, label_smoothing=pm.getLabelSmoothing())
+                              MOVING_AVERAGE_DECAY, label_smoothing=pm.getLabelSmoothing(),
+                              # data parallel: rank r draws its own masks from dropout_seed + r (no state to broadcast)
+                              dropout=pm.getDropout(),
+                              dropout_seed=pm.getDropoutSeed(FLAGS.seed) + (cl.rank if cl.mode == "dp" else 0))
     init = torch_ref.init_params(spec, seed=FLAGS.seed)
     if cl.mode == "ps" and cl.job_name == "ps":
         from ..ckpt.saver import Saver, latest_checkpoint

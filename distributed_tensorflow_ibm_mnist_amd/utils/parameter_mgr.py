@@ -17,6 +17,8 @@ overrides:
     getValData()             -> list[str]
     getOptimizer(lr)         -> OptimizerSpec
     getLabelSmoothing()      -> float   (eps of the smoothed training targets; 0.0: hard labels)
+    getDropout()             -> float   (drop rate of the hidden dense layers; 0.0: off)
+    getDropoutSeed(default)  -> int     (seed of the dropout masks; unset: ``default``, the run's seed)
 
 Defaults are the TF CIFAR-10 tutorial values that ``mnist_input.py`` mirrors
  — they are *chosen* defaults, not numbers the reference
@@ -55,6 +57,8 @@ DEFAULTS: Dict[str, Any] = {
     "lr_end": 0.0,               # polynomial | cosine: the rate from lr_total_steps on
     "lr_power": 1.0,             # polynomial: the exponent
     "label_smoothing": 0.0,      # training loss against (1 - eps) * onehot + eps / classes; 0: hard labels
+    "dropout": 0.0,              # drop rate on the hidden ReLU dense layers' outputs (training only); 0: off
+    "dropout_seed": None,        # seed of the counter-based dropout masks; None: the run's seed
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -139,7 +143,7 @@ def configure(source: Union[None, str, Dict[str, Any]] = None, **overrides: Any)
 FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", "optimizer", "momentum",
              "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
              "adagrad_initial_accumulator", "clip_norm", "lars_eta", "lr_schedule", "warmup_steps",
-             "lr_total_steps", "lr_end", "lr_power", "label_smoothing")
+             "lr_total_steps", "lr_end", "lr_power", "label_smoothing", "dropout", "dropout_seed")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
@@ -251,6 +255,28 @@ def getLabelSmoothing() -> float:
     if not 0 <= eps < 1:       # NaN fails both comparisons
         raise ValueError(f"label_smoothing must be finite with 0 <= label_smoothing < 1, got {eps}")
     return eps
+
+
+def getDropout() -> float:
+    """The ``dropout`` key: the drop rate (as ``torch.nn.Dropout``), finite with 0 <= p < 1."""
+    from ..ops.dropout import check_rate
+    return check_rate(get("dropout"), "dropout")
+
+
+def getDropoutSeed(default: int = 0) -> int:
+    """The ``dropout_seed`` key: an integer with 0 <= seed < 2^63; unset: ``default`` (the run's seed)."""
+    from ..ops.dropout import check_seed
+    v = get("dropout_seed")
+    return check_seed(default if v is None else v, "dropout_seed")
+
+
+def check_ps_dropout(job_name: str, log=print) -> None:
+    """The dropout masks are drawn from the device-side global step, and a parameter-server worker's
+    device step is not the global step: a PS or worker task with ``dropout`` > 0 exits at start-up."""
+    if job_name in ("ps", "worker") and getDropout() > 0:
+        log(f"dropout is not supported in parameter-server mode (--job_name={job_name}): the masks follow the "
+            f"device-side global step, which a worker does not hold; dropout runs single-process and data-parallel")
+        raise SystemExit(2)
 
 
 def check_ps_lr_schedule(job_name: str, log=print) -> None:

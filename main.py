@@ -59,6 +59,9 @@ flags.DEFINE_float("lr_end", -1, "polynomial | cosine: the rate from --lr_total_
 flags.DEFINE_float("lr_power", -1, "polynomial: the exponent (1.0)")
 flags.DEFINE_float("label_smoothing", -1, "train against (1 - eps) * onehot + eps / classes, 0 <= eps < 1 (0.0: hard "
                    "labels); the training cross_entropy / total_loss are the smoothed loss, every eval stays plain")
+flags.DEFINE_float("dropout", -1, "drop rate 0 <= p < 1 on the hidden ReLU dense layers' outputs, training only (0.0: "
+                   "off; -1: unset); masks from a counter-based RNG on the device; not in parameter-server mode")
+flags.DEFINE_integer("dropout_seed", -1, "seed of the dropout masks (-1: unset, the run's --seed); rank r uses seed + r")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
@@ -104,13 +107,14 @@ flags.DEFINE_float("collective_timeout", 600.0, "process-group timeout (s): a hu
 
 
 def main(argv=None):
-    # a PS / worker task with an adaptive optimizer, clip_norm, a warmup or a schedule other than the
-    # staircase stops here, before torch is even imported
+    # a PS / worker task with an adaptive optimizer, clip_norm, dropout, a warmup or a schedule other
+    # than the staircase stops here, before torch is even imported
     from distributed_tensorflow_ibm_mnist_amd.utils import parameter_mgr
     parameter_mgr.configure_from_flags(FLAGS)
     parameter_mgr.check_ps_optimizer(FLAGS.job_name)
     parameter_mgr.check_ps_clip_norm(FLAGS.job_name)
     parameter_mgr.check_ps_lr_schedule(FLAGS.job_name)
+    parameter_mgr.check_ps_dropout(FLAGS.job_name)
     if FLAGS.ps_hosts and FLAGS.job_name in ("ps", "worker") and "GPU_MAX_HW_QUEUES" not in os.environ:
         # PS mode only (data-parallel workers keep HIP's default queues, so the RCCL stream
         # does not share a queue with compute): PS tasks are often co-located on one GPU,
