@@ -51,6 +51,10 @@ def parse(argv=None):
                     help="train against (1 - eps) * onehot + eps / 10; the accuracy probe is an eval and unaffected")
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="drop rate on the hidden dense layers, training only; the accuracy probe is an eval")
+    ap.add_argument("--augment_shift", type=int, default=0,
+                    help="random translation of the training images, pixels (0..8); the accuracy probe is an eval")
+    ap.add_argument("--augment_rotate", type=float, default=0.0, help="random rotation, degrees (0..180)")
+    ap.add_argument("--augment_scale", type=float, default=0.0, help="random zoom in [1 - z, 1 + z) (0..0.5)")
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
     ap.add_argument("--probe", type=int, default=10000, help="training images in the accuracy probe")
@@ -124,9 +128,12 @@ def run(args) -> dict:
     # --fused_input: the first fused conv reads the uint8 dataset through the batch index
     # (K10 fused).  Off by default: measured ~25 us/step slower on LeNet-5 at 65536 than
     # prep_images + bf16 (profiles/r1_u8_input/).
-    fused_in = args.impl == "hip" and args.fused_input and net.bind_u8_input(ds.images)
+    from distributed_tensorflow_ibm_mnist_amd.data.augment import AugmentConfig
+    aug = AugmentConfig(args.augment_shift, args.augment_rotate, args.augment_scale, args.seed)
+    # augmentation writes the input buffer itself: no fused gather of un-augmented rows
+    fused_in = args.impl == "hip" and args.fused_input and not aug.enabled and net.bind_u8_input(ds.images)
     loader = DeviceLoader(ds, net.x0, net.labels, rank=rank, world=world, seed=args.seed,
-                          idx_out=net.idx_buf if fused_in else None)
+                          idx_out=net.idx_buf if fused_in else None, augment=aug)
 
     graph = None
     if args.graph and args.impl == "hip" and world == 1 and dev.type == "cuda":
@@ -184,6 +191,7 @@ def run(args) -> dict:
                    "lr": args.lr, "lr_schedule": opt.schedule, "warmup_steps": opt.warmup_steps,
                    "lr_total_steps": opt.total_steps, "lr_end": opt.lr_end, "lr_power": opt.lr_power,
                    "label_smoothing": opt.label_smoothing, "dropout": opt.dropout,
+                   "augment": [aug.shift, aug.rotate, aug.scale],
                    "eval_every": args.eval_every, "impl": args.impl, "hip_graph": graph is not None,
                    "parallelism": f"dp{world}"},
         "history": history[-20:],

@@ -272,6 +272,62 @@ void prep_images(Tensor src, Tensor idx, Tensor lab_src, Tensor out, Tensor lab_
          "prep_images");
 }
 
+// the augmentation keys (augment.hip): a ValueError naming key and value, as data/augment.py raises
+void augment_keys(const char* op, int64_t pos0, int64_t n, int64_t seed, int64_t shift, double rotate, double scale) {
+  TORCH_CHECK_VALUE(shift >= 0 && shift <= mnistx::AUG_MAX_SHIFT, op,
+                    ": augment_shift must be an integer with 0 <= augment_shift <= 8, got ", shift);
+  TORCH_CHECK_VALUE(std::isfinite(rotate) && rotate >= 0.0 && rotate <= (double)mnistx::AUG_MAX_ROTATE, op,
+                    ": augment_rotate must be finite with 0 <= augment_rotate <= 180, got ", rotate);
+  TORCH_CHECK_VALUE(std::isfinite(scale) && scale >= 0.0 && scale <= (double)mnistx::AUG_MAX_SCALE, op,
+                    ": augment_scale must be finite with 0 <= augment_scale <= 0.5, got ", scale);
+  TORCH_CHECK_VALUE(seed >= 0, op, ": augment_seed must be an integer with 0 <= augment_seed < 2^63, got ", seed);
+  TORCH_CHECK_VALUE(pos0 >= 0 && pos0 <= INT64_MAX - n, op, ": pos0 must be >= 0 with pos0 + n below 2^63, got ", pos0);
+}
+
+void augment_images(Tensor src, Tensor idx, Tensor lab_src, Tensor out, Tensor lab_out, int64_t Csrc, int64_t Cdst,
+                    int64_t pos0, int64_t seed, int64_t shift, double rotate, double scale) {
+  const int64_t nb = idx.numel();
+  augment_keys("augment_images", pos0, nb, seed, shift, rotate, scale);
+  TORCH_CHECK((Csrc == 1 && Cdst == 1) || (Csrc == 3 && Cdst == 3) || (Csrc == 1 && Cdst == 3),
+              "augment_images: (Csrc, Cdst) must be (1, 1), (3, 3) or (1, 3), got (", Csrc, ", ", Cdst, ")");
+  TORCH_CHECK(src.dim() == 2 && src.size(1) == 784 * Csrc, "augment_images: src must be a [N, ", 784 * Csrc,
+              "] uint8 dataset");
+  const int64_t N = src.size(0);
+  check(src, at::kByte, N * 784 * Csrc, "src");
+  check(idx, at::kLong, nb, "idx");
+  check(lab_src, at::kInt, N, "lab_src");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat,
+              "augment_images: out must be bf16 or fp32, got ", out.scalar_type());
+  TORCH_CHECK(out.dim() >= 1 && nb <= out.size(0), "augment_images: ", nb, " indices for an out of ",
+              out.dim() >= 1 ? out.size(0) : 0, " rows");
+  TORCH_CHECK(out.dim() >= 1 && out.numel() == out.size(0) * 784 * Cdst, "augment_images: out must be [B, 784 * ", Cdst,
+              "]");
+  check(out, out.scalar_type(), nb * 784 * Cdst, "out");
+  check(lab_out, at::kInt, nb, "lab_out");
+  TORCH_CHECK(nb < ((int64_t)1 << 31) / (784 * 3), "augment_images: batch too large");
+  TORCH_CHECK(idx.device() == src.device() && lab_src.device() == src.device() && out.device() == src.device() &&
+                  lab_out.device() == src.device(),
+              "augment_images: every buffer must be on one device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "augment_images: src and out must be 16-byte aligned");
+  hip_ok(mnistx::augment_images(P<const uint8_t>(src), P<const int64_t>(idx), P<const int32_t>(lab_src), (int)nb,
+                                (int)Csrc, (int)Cdst, pos0, seed, (int)shift, (float)rotate, (float)scale,
+                                out.data_ptr(), out.scalar_type() == at::kFloat, P<int32_t>(lab_out), cur_stream()),
+         "augment_images");
+}
+
+// (tx, ty, theta, s) of positions pos0 .. pos0 + n - 1 as augment_images draws them: out fp32 [n, 4]
+void augment_params(Tensor out, int64_t pos0, int64_t seed, int64_t shift, double rotate, double scale) {
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == 4, "augment_params: out must be [n, 4] fp32");
+  const int64_t n = out.size(0);
+  augment_keys("augment_params", pos0, n, seed, shift, rotate, scale);
+  check(out, at::kFloat, n * 4, "out");
+  TORCH_CHECK(n < ((int64_t)1 << 31), "augment_params: n too large");
+  hip_ok(mnistx::augment_params(P<float>(out), (int)n, pos0, seed, (int)shift, (float)rotate, (float)scale,
+                                cur_stream()),
+         "augment_params");
+}
+
 void maxpool_fwd(Tensor x, Tensor y, Tensor arg, int64_t Nb, int64_t H, int64_t W, int64_t C, int64_t OH,
                  int64_t OW) {
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
@@ -1727,6 +1783,11 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("seed"), py::arg("layer"), py::arg("p"));
   m.def("dropout_mask", &dropout_mask, py::arg("out"), py::arg("nb"), py::arg("n"), py::arg("step"), py::arg("seed"),
         py::arg("layer"), py::arg("p"));
+  m.def("augment_images", &augment_images, py::arg("src"), py::arg("idx"), py::arg("lab_src"), py::arg("out"),
+        py::arg("lab_out"), py::arg("Csrc"), py::arg("Cdst"), py::arg("pos0"), py::arg("seed"), py::arg("shift"),
+        py::arg("rotate"), py::arg("scale"));
+  m.def("augment_params", &augment_params, py::arg("out"), py::arg("pos0"), py::arg("seed"), py::arg("shift"),
+        py::arg("rotate"), py::arg("scale"));
   m.def("fused_optimizer", &fused_optimizer, py::arg("params"), py::arg("grads"), py::arg("mom"), py::arg("ema"),
         py::arg("bf"), py::arg("segs"), py::arg("step"), py::arg("lr0"), py::arg("decay_rate"),
         py::arg("decay_steps"), py::arg("momentum"), py::arg("nesterov"), py::arg("use_momentum"),

@@ -355,6 +355,19 @@ hipError_t dropout_bwd(bf16_t* dy, int64_t nb, int n, int ld, const int64_t* ste
 // the keep bits themselves, uint8 [nb, n] (what lr_at_steps is to the schedule: for the tests)
 hipError_t dropout_mask(uint8_t* out, int64_t nb, int n, const int64_t* step, uint64_t seed, int layer, uint32_t thr,
                         hipStream_t st);
+// Training augmentation (augment.hip): the K10 slot with a random shift of up to S whole pixels, a
+// rotation of up to R degrees and a zoom in [1 - Z, 1 + Z) per image, drawn from (seed, pos0 + b) by
+// Philox4x32-10; bilinear, zero fill.  out [nb, 784, Cdst] bf16 or fp32 (out_f32) and lab_out [nb]
+// are written for rows < nb only; src [N, 784 * Csrc] and out 16-byte aligned; (Csrc, Cdst) in
+// {(1, 1), (3, 3), (1, 3)}.  S = R = Z = 0 writes bitwise what prep_images writes.
+constexpr int AUG_MAX_SHIFT = 8;
+constexpr float AUG_MAX_ROTATE = 180.f, AUG_MAX_SCALE = 0.5f;
+hipError_t augment_images(const uint8_t* src, const int64_t* idx, const int32_t* lab_src, int nb, int Csrc, int Cdst,
+                          int64_t pos0, int64_t seed, int S, float R, float Z, void* out, bool out_f32,
+                          int32_t* lab_out, hipStream_t st);
+// (tx, ty, theta, s) of positions pos0 .. pos0 + n - 1 as augment_images draws them, fp32 [n, 4]
+// (what dropout_mask is to dropout: for the tests)
+hipError_t augment_params(float* out, int n, int64_t pos0, int64_t seed, int S, float R, float Z, hipStream_t st);
 // NOTE: many splits over a small output are pre-summed IN PLACE (the slab is scratch).
 hipError_t splitk_reduce(float* slab, int splits, int M, int N, int G, int Ipad, int I, int J,
                          int bias_row, float* wdst, float* bdst, float scale, hipStream_t st);

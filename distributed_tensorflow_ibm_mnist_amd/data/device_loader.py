@@ -23,6 +23,8 @@ from typing import Iterator, Optional, Tuple
 import torch
 
 from ..ops._ext import kernels
+from . import augment as aug
+from .augment import AugmentConfig
 
 
 def gather_into(ds: "DeviceDataset", idx: torch.Tensor, out_images: torch.Tensor, out_labels: torch.Tensor) -> None:
@@ -39,6 +41,24 @@ def gather_into(ds: "DeviceDataset", idx: torch.Tensor, out_images: torch.Tensor
     if ds.channels != cdst:
         x = x[..., :1].expand(nb, ds.hw, cdst)
     out_images.view(-1)[: nb * ds.hw * cdst].copy_(x.reshape(-1))
+    out_labels[:nb].copy_(ds.labels[idx])
+
+
+def augment_into(ds: "DeviceDataset", idx: torch.Tensor, out_images: torch.Tensor, out_labels: torch.Tensor,
+                 cfg: AugmentConfig, pos0: int) -> None:
+    """``gather_into`` with the training augmentation of ``data/augment.py``: batch entry b is drawn
+    from ``(cfg.seed, pos0 + b)``.  The ``augment_images`` HIP kernel on the GPU; on CPU the host
+    reference ``warp`` rounded once to the buffer's dtype."""
+    cdst = int(out_images.shape[-1])
+    nb = idx.numel()
+    if ds.device.type == "cuda":
+        kernels().augment_images(ds.images, idx, ds.labels, out_images, out_labels, ds.channels, cdst, int(pos0),
+                                 cfg.seed, cfg.shift, cfg.rotate, cfg.scale)
+        return
+    x = aug.warp(ds.images[idx].numpy(), aug.params(cfg, pos0, nb), ds.channels, cdst)
+    # one rounding of the float64 value: straight to fp32, or to bf16 through fp32 rounded to odd
+    x = x.astype("float32") if out_images.dtype == torch.float32 else aug.f32_round_to_odd(x)
+    out_images.view(-1)[: nb * ds.hw * cdst].copy_(torch.from_numpy(x).reshape(-1))
     out_labels[:nb].copy_(ds.labels[idx])
 
 
@@ -135,10 +155,25 @@ def perm_positions(start: int, n: int, N: int, seed: int, device=None, out: Opti
 class DeviceLoader:
     def __init__(self, ds: DeviceDataset, out_images: torch.Tensor, out_labels: torch.Tensor, rank: int = 0,
                  world: int = 1, seed: int = 0, shard: bool = True, shuffle: bool = True,
-                 idx_out: Optional[torch.Tensor] = None):
+                 idx_out: Optional[torch.Tensor] = None, augment: Optional[AugmentConfig] = None):
         """``idx_out``: instead of gathering + normalising images into ``out_images``,
         write the batch's dataset indices there (the first fused conv reads the
-        uint8 dataset itself: HipNet.bind_u8_input); labels are still gathered."""
+        uint8 dataset itself: HipNet.bind_u8_input); labels are still gathered.
+        ``augment``: every batch entry is shifted / rotated / zoomed as ``data/augment.py``
+        draws it from (seed, global stream position); the rows are the ones an un-augmented
+        loader gathers.  Needs the gathered-image path (``idx_out`` None); a config with all
+        three amounts 0 is no augmentation."""
+        if augment is not None and not augment.enabled:
+            augment = None
+        if augment is not None and idx_out is not None:
+            raise ValueError("augment needs the gathered-image input path: idx_out must be None (a fused first "
+                             "conv gathers un-augmented dataset rows)")
+        if augment is not None and (ds.hw != 784 or (ds.channels, int(out_images.shape[-1])) not in ((1, 1), (3, 3), (1, 3))):
+            raise ValueError(f"augment needs 28x28 images with (Csrc, Cdst) in (1, 1), (3, 3), (1, 3), got hw={ds.hw}, "
+                             f"({ds.channels}, {int(out_images.shape[-1])})")
+        if augment is not None and not shard:   # unsharded ranks: own transformations, as own orders
+            augment = augment.with_seed((augment.seed + 7919 * rank) % (1 << 63))
+        self.augment = augment
         self.ds, self.out_images, self.out_labels = ds, out_images, out_labels
         self.idx_out = idx_out
         self.B = int(out_labels.shape[0])
@@ -166,6 +201,8 @@ class DeviceLoader:
         nothing.  Only for the resident-dataset shuffle (``idx_out``) with full batches, and
         only where nothing else writes the index / label buffers between the optimizer and
         the next ``next()`` (bench.py; not the CLI loop, which evaluates into them)."""
+        if self.augment is not None:
+            return None
         if not (self.shuffle and self.idx_out is not None and self.idx_out.is_cuda and self.ds.device.type == "cuda"):
             return None
         N = len(self.ds)
@@ -183,6 +220,16 @@ class DeviceLoader:
             return nb
         start = self.pos + (self.rank * self.B if self.shard else 0)
         N = len(self.ds)
+        if self.augment is not None:
+            # the rows of the plain paths (Feistel or sequential), then one kernel: gather + transform +
+            # normalise (+ labels)
+            if self.shuffle:
+                idx = perm_positions(start, nb, N, self.seed, out=self.idx)
+            else:
+                idx = torch.remainder(torch.arange(start, start + nb, device=self.ds.device), N)
+            augment_into(self.ds, idx, self.out_images, self.out_labels, self.augment, start)
+            self.pos += self.global_batch
+            return nb
         if (self.shuffle and self.idx_out is None and self.ds.device.type == "cuda" and self.ds.hw == 784
                 and self.ds.channels == 1 and self.cdst == 1 and self.out_images.dtype == torch.bfloat16):
             # one kernel: Feistel row + gather + normalise (+ labels)

@@ -101,7 +101,9 @@ class Replica:
                  eval_images: Optional[torch.Tensor] = None, eval_labels: Optional[torch.Tensor] = None,
                  seed: int = 0, shard: bool = True, use_graph: bool = True, bucket_mb: float = 4.0,
                  group=None, standalone: bool = False, fused_input=False, precision: str = "bf16",
-                 dp_graph: bool = False):
+                 dp_graph: bool = False, augment=None, log=print):
+        """``augment``: a ``data.augment.AugmentConfig``; when any of its amounts is non-zero the
+        training batches (and only those) are shifted / rotated / zoomed on the device."""
         self.spec, self.impl, self.B, self.device = spec, impl, batch, torch.device(device)
         self.net = build_net(impl, spec, batch, self.device, init, opt, precision)
         # standalone: a parameter-server worker (no data-parallel group of its own)
@@ -115,13 +117,19 @@ class Replica:
         # --input_mode u8 / bf16 (HIP; --fused_input = u8): the first fused conv gathers the
         # resident training set (uint8, or normalised once to bf16) through the batch index
         mode = "u8" if fused_input is True else (fused_input or "prep")
+        self.augment = augment if augment is not None and augment.enabled else None
+        if self.augment is not None and mode != "prep":
+            # the first fused conv can only gather un-augmented dataset rows
+            log(f"augmentation is on: input mode {mode!r} -> 'prep' (the augmentation kernel writes the input buffer)")
+            mode = "prep"
         # eligibility first: a model that cannot gather (3-channel input, fp32 executor) never
         # gets a normalised bf16 copy of the whole split built for nothing
         fused_in = (impl == "hip" and mode != "prep" and getattr(self.net, "can_gather_input", lambda: True)()
                     and self.net.bind_u8_input(self.train_ds.images if mode == "u8" else self.train_ds.bf16_images(),
                                                 bwd_images=None if mode == "u8" else self.train_ds.images))
         self.loader = DeviceLoader(self.train_ds, self.net.x0, self.net.labels, rank=self.rank, world=self.world,
-                                   seed=seed, shard=shard, idx_out=self.net.idx_buf if fused_in else None)
+                                   seed=seed, shard=shard, idx_out=self.net.idx_buf if fused_in else None,
+                                   augment=self.augment)
         # hipGraph: single replica, or (dp_graph) the DP step with its RCCL all-reduces captured
         self.use_graph = (use_graph and impl == "hip" and self.device.type == "cuda"
                           and (self.world == 1 or (dp_graph and dist.get_backend(group) == "nccl")))

@@ -109,6 +109,9 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
                               # data parallel: rank r draws its own masks from dropout_seed + r (no state to broadcast)
                               dropout=pm.getDropout(),
                               dropout_seed=pm.getDropoutSeed(FLAGS.seed) + (cl.rank if cl.mode == "dp" else 0))
+    # training-input augmentation: drawn per (augment_seed, stream position), so sharded ranks differ
+    # without a per-rank seed (an unsharded loader offsets the seed itself, as it does for the shuffle)
+    augment = pm.getAugment(FLAGS.seed)
     init = torch_ref.init_params(spec, seed=FLAGS.seed)
     if cl.mode == "ps" and cl.job_name == "ps":
         from ..ckpt.saver import Saver, latest_checkpoint
@@ -140,8 +143,9 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
                    seed=FLAGS.seed, shard=not FLAGS.no_shard, use_graph=FLAGS.hip_graph,
                    bucket_mb=FLAGS.bucket_mb, group=dp_group if cl.mode == "dp" else None,
                    fused_input=True if FLAGS.fused_input else getattr(FLAGS, "input_mode", "prep"), precision=getattr(FLAGS, "precision", "bf16"),
-                   dp_graph=getattr(FLAGS, "hip_graph_dp", False)) \
-        if cl.mode != "ps" else _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS)
+                   dp_graph=getattr(FLAGS, "hip_graph_dp", False), augment=augment, log=log) \
+        if cl.mode != "ps" else _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS,
+                                         augment, log)
     replica = base
     if cl.mode == "ps":
         from ..parallel.ps import PSWorkerReplica
@@ -206,8 +210,13 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
     return res
 
 
-def _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS):
-    """A PS-mode worker: own input stream (reference P3: no sharding), no DP group."""
+def _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS, augment=None, log=print):
+    """A PS-mode worker: own input stream (reference P3: no sharding), no DP group.  It owns its
+    loader, so it augments its own inputs; the servers never see them."""
+    if augment is not None and augment.enabled:
+        # a standalone replica is rank 0 of its own world: the task id separates the workers' draws,
+        # as it separates their data orders
+        augment = augment.with_seed((augment.seed + 7919 * cl.task_id) % (1 << 63))
     return Replica(spec, impl, batch_size, cl.device, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev,
                    seed=FLAGS.seed + 7919 * cl.task_id, shard=False, use_graph=False, bucket_mb=FLAGS.bucket_mb,
-                   standalone=True, precision=getattr(FLAGS, "precision", "bf16"))
+                   standalone=True, precision=getattr(FLAGS, "precision", "bf16"), augment=augment, log=log)

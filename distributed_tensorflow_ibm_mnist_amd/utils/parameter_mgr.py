@@ -19,6 +19,9 @@ overrides:
     getLabelSmoothing()      -> float   (eps of the smoothed training targets; 0.0: hard labels)
     getDropout()             -> float   (drop rate of the hidden dense layers; 0.0: off)
     getDropoutSeed(default)  -> int     (seed of the dropout masks; unset: ``default``, the run's seed)
+    getAugmentShift() / getAugmentRotate() / getAugmentScale() / getAugmentSeed(default)
+                             -> int / float / float / int   (training-input augmentation; 0: off)
+    getAugment(default_seed) -> AugmentConfig   (the four keys, checked)
 
 Defaults are the TF CIFAR-10 tutorial values that ``mnist_input.py`` mirrors
  — they are *chosen* defaults, not numbers the reference
@@ -59,6 +62,10 @@ DEFAULTS: Dict[str, Any] = {
     "label_smoothing": 0.0,      # training loss against (1 - eps) * onehot + eps / classes; 0: hard labels
     "dropout": 0.0,              # drop rate on the hidden ReLU dense layers' outputs (training only); 0: off
     "dropout_seed": None,        # seed of the counter-based dropout masks; None: the run's seed
+    "augment_shift": 0,          # training images: random translation of up to this many whole pixels (0..8); 0: off
+    "augment_rotate": 0.0,       # ... random rotation about the centre of up to this many degrees (0..180); 0: off
+    "augment_scale": 0.0,        # ... random zoom in [1 - z, 1 + z) (0..0.5); 0: off
+    "augment_seed": None,        # seed of the counter-based augmentation draws; None: the run's seed
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -143,7 +150,8 @@ def configure(source: Union[None, str, Dict[str, Any]] = None, **overrides: Any)
 FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", "optimizer", "momentum",
              "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
              "adagrad_initial_accumulator", "clip_norm", "lars_eta", "lr_schedule", "warmup_steps",
-             "lr_total_steps", "lr_end", "lr_power", "label_smoothing", "dropout", "dropout_seed")
+             "lr_total_steps", "lr_end", "lr_power", "label_smoothing", "dropout", "dropout_seed",
+             "augment_shift", "augment_rotate", "augment_scale", "augment_seed")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
@@ -268,6 +276,39 @@ def getDropoutSeed(default: int = 0) -> int:
     from ..ops.dropout import check_seed
     v = get("dropout_seed")
     return check_seed(default if v is None else v, "dropout_seed")
+
+
+def getAugmentShift() -> int:
+    """The ``augment_shift`` key: an integer with 0 <= S <= 8, the largest translation in pixels."""
+    from ..data.augment import check_shift
+    return check_shift(get("augment_shift"), "augment_shift")
+
+
+def getAugmentRotate() -> float:
+    """The ``augment_rotate`` key: finite with 0 <= R <= 180, the largest rotation in degrees."""
+    from ..data.augment import check_rotate
+    return check_rotate(get("augment_rotate"), "augment_rotate")
+
+
+def getAugmentScale() -> float:
+    """The ``augment_scale`` key: finite with 0 <= Z <= 0.5, the zoom is drawn from [1 - Z, 1 + Z)."""
+    from ..data.augment import check_scale
+    return check_scale(get("augment_scale"), "augment_scale")
+
+
+def getAugmentSeed(default: int = 0) -> int:
+    """The ``augment_seed`` key: an integer with 0 <= seed < 2^63; unset: ``default`` (the run's seed)."""
+    from ..ops.dropout import check_seed
+    v = get("augment_seed")
+    return check_seed(default if v is None else v, "augment_seed")
+
+
+def getAugment(default_seed: int = 0):
+    """The four augmentation keys as a ``data.augment.AugmentConfig`` (its ``enabled`` says whether any
+    amount is non-zero).  The workers augment their own inputs and the servers never see inputs, so
+    parameter-server mode takes the keys as they are."""
+    from ..data.augment import AugmentConfig
+    return AugmentConfig(getAugmentShift(), getAugmentRotate(), getAugmentScale(), getAugmentSeed(default_seed))
 
 
 def check_ps_dropout(job_name: str, log=print) -> None:

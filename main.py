@@ -62,6 +62,14 @@ flags.DEFINE_float("label_smoothing", -1, "train against (1 - eps) * onehot + ep
 flags.DEFINE_float("dropout", -1, "drop rate 0 <= p < 1 on the hidden ReLU dense layers' outputs, training only (0.0: "
                    "off; -1: unset); masks from a counter-based RNG on the device; not in parameter-server mode")
 flags.DEFINE_integer("dropout_seed", -1, "seed of the dropout masks (-1: unset, the run's --seed); rank r uses seed + r")
+flags.DEFINE_integer("augment_shift", -1, "training images only: random translation of up to this many whole pixels, "
+                     "0..8, independently in x and y (0: off; -1: unset)")
+flags.DEFINE_float("augment_rotate", -1, "training images only: random rotation about the image centre of up to this "
+                   "many degrees, 0..180 (0.0: off; -1: unset)")
+flags.DEFINE_float("augment_scale", -1, "training images only: random zoom drawn from [1 - z, 1 + z), 0..0.5 (0.0: off; "
+                   "-1: unset); any of the three on trains in --input_mode prep")
+flags.DEFINE_integer("augment_seed", -1, "seed of the augmentation draws (-1: unset, the run's --seed); a draw is a "
+                     "function of (seed, stream position), so a resumed run repeats it")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
