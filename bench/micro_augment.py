@@ -4,6 +4,9 @@ LeNet-5 training step with augmentation on against the same step in the prep and
 (HIP events; one JSON line at the end).
 Usage: python bench/micro_augment.py [--rounds 5] [--iters 100] [--batch 65536] [--step_iters 20]
                                      [--shift 2 --rotate 15 --scale 0.15] [--no_step]
+                                     [--elastic_alpha 34 --elastic_sigma 4]
+With --elastic_alpha > 0 the elastic form (augment_elastic.hip) is timed as a third kernel next to the
+affine one, alternating in the same process, and a fourth Replica trains with affine + elastic.
 * kernels: `augment_images` and `prep_images` on the same random rows of a 60000-image uint8 dataset,
   alternating windows of `iters` back-to-back launches in one process, at out [65536, 784, 1] bf16 and
   (1 -> 3 channels) [16384, 784, 3] bf16: median us of each, their ratio, achieved GB/s (both read one
@@ -15,7 +18,7 @@ Usage: python bench/micro_augment.py [--rounds 5] [--iters 100] [--batch 65536] 
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from distributed_tensorflow_ibm_mnist_amd.data.augment import AugmentConfig
+from distributed_tensorflow_ibm_mnist_amd.data.augment import AugmentConfig, elastic_weights
 from distributed_tensorflow_ibm_mnist_amd.models import get_model, torch_ref
 from distributed_tensorflow_ibm_mnist_amd.ops._ext import kernels
 from distributed_tensorflow_ibm_mnist_amd.runtime.params import OptConfig
@@ -29,12 +32,16 @@ ap.add_argument("--step_iters", type=int, default=20)
 ap.add_argument("--shift", type=int, default=2)
 ap.add_argument("--rotate", type=float, default=15.0)
 ap.add_argument("--scale", type=float, default=0.15)
+ap.add_argument("--elastic_alpha", type=float, default=0.0)
+ap.add_argument("--elastic_sigma", type=float, default=4.0)
 ap.add_argument("--no_step", action="store_true")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 K = kernels()
 N = 60000
-out = {"rounds": args.rounds, "augment": [args.shift, args.rotate, args.scale]}
+out = {"rounds": args.rounds, "augment": [args.shift, args.rotate, args.scale],
+       "elastic": [args.elastic_alpha, args.elastic_sigma]}
+table = torch.from_numpy(elastic_weights(args.elastic_sigma).copy()) if args.elastic_alpha > 0 else None
 
 
 def timed(fn, iters):
@@ -57,6 +64,10 @@ for nb, cd in ((65536, 1), (16384, 3)):
     fns = {"prep_images": lambda: K.prep_images(src, idx, lab, x, lo, 784, 1, cd),
            "augment_images": lambda: K.augment_images(src, idx, lab, x, lo, 1, cd, 12345, 7, args.shift, args.rotate,
                                                       args.scale)}
+    if table is not None:
+        fns["augment_images_elastic"] = lambda: K.augment_images(src, idx, lab, x, lo, 1, cd, 12345, 7, args.shift,
+                                                                 args.rotate, args.scale, elastic_alpha=args.elastic_alpha,
+                                                                 elastic_weights=table)
     us = {k: [] for k in fns}
     for fn in fns.values():
         timed(fn, 10)
@@ -71,6 +82,9 @@ for nb, cd in ((65536, 1), (16384, 3)):
         res[k] = {"us": med, "min": min(t), "max": max(t), "GBps": gbs}
     res["ratio"] = res["augment_images"]["us"] / res["prep_images"]["us"]
     print(f"  augment_images / prep_images = {res['ratio']:.2f}")
+    if table is not None:
+        res["elastic_ratio"] = res["augment_images_elastic"]["us"] / res["augment_images"]["us"]
+        print(f"  augment_images with elastic / without = {res['elastic_ratio']:.2f}")
     out[f"{nb}x784x{cd}"] = res
 
 if not args.no_step:
@@ -79,7 +93,11 @@ if not args.no_step:
     B = args.batch
     cfg = AugmentConfig(args.shift, args.rotate, args.scale, 7)
     reps = {}
-    for name, mode, aug in (("augment", "bf16", cfg), ("prep", "prep", None), ("bf16", "bf16", None)):
+    variants = [("augment", "bf16", cfg), ("prep", "prep", None), ("bf16", "bf16", None)]
+    if table is not None:
+        variants.insert(0, ("elastic", "bf16", AugmentConfig(args.shift, args.rotate, args.scale, 7, args.elastic_alpha,
+                                                             args.elastic_sigma)))
+    for name, mode, aug in variants:
         reps[name] = Replica(spec, "hip", B, dev, init, OptConfig(lr0=0.01, use_momentum=True, momentum=0.9), src.cpu(),
                              lab.cpu(), 1, seed=0, use_graph=True, fused_input=mode, augment=aug)
         timed(reps[name].step, 5)

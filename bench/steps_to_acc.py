@@ -55,6 +55,10 @@ def parse(argv=None):
                     help="random translation of the training images, pixels (0..8); the accuracy probe is an eval")
     ap.add_argument("--augment_rotate", type=float, default=0.0, help="random rotation, degrees (0..180)")
     ap.add_argument("--augment_scale", type=float, default=0.0, help="random zoom in [1 - z, 1 + z) (0..0.5)")
+    ap.add_argument("--augment_elastic_alpha", type=float, default=0.0,
+                    help="elastic distortion: displacement scale of the smoothed random field, pixels (0..64)")
+    ap.add_argument("--augment_elastic_sigma", type=float, default=4.0,
+                    help="elastic distortion: standard deviation of the smoothing Gaussian, pixels (0.5..8)")
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
     ap.add_argument("--probe", type=int, default=10000, help="training images in the accuracy probe")
@@ -129,7 +133,8 @@ def run(args) -> dict:
     # (K10 fused).  Off by default: measured ~25 us/step slower on LeNet-5 at 65536 than
     # prep_images + bf16 (profiles/r1_u8_input/).
     from distributed_tensorflow_ibm_mnist_amd.data.augment import AugmentConfig
-    aug = AugmentConfig(args.augment_shift, args.augment_rotate, args.augment_scale, args.seed)
+    aug = AugmentConfig(args.augment_shift, args.augment_rotate, args.augment_scale, args.seed,
+                        args.augment_elastic_alpha, args.augment_elastic_sigma)
     # augmentation writes the input buffer itself: no fused gather of un-augmented rows
     fused_in = args.impl == "hip" and args.fused_input and not aug.enabled and net.bind_u8_input(ds.images)
     loader = DeviceLoader(ds, net.x0, net.labels, rank=rank, world=world, seed=args.seed,
@@ -192,6 +197,7 @@ def run(args) -> dict:
                    "lr_total_steps": opt.total_steps, "lr_end": opt.lr_end, "lr_power": opt.lr_power,
                    "label_smoothing": opt.label_smoothing, "dropout": opt.dropout,
                    "augment": [aug.shift, aug.rotate, aug.scale],
+                   "augment_elastic": [aug.elastic_alpha, aug.elastic_sigma],
                    "eval_every": args.eval_every, "impl": args.impl, "hip_graph": graph is not None,
                    "parallelism": f"dp{world}"},
         "history": history[-20:],

@@ -284,10 +284,37 @@ void augment_keys(const char* op, int64_t pos0, int64_t n, int64_t seed, int64_t
   TORCH_CHECK_VALUE(pos0 >= 0 && pos0 <= INT64_MAX - n, op, ": pos0 must be >= 0 with pos0 + n below 2^63, got ", pos0);
 }
 
+// the elastic keys: the displacement scale, and the half table of the smoothing Gaussian as
+// data/augment.py elastic_weights computes it (its one source: the kernels take the table, not sigma)
+void elastic_alpha_ok(const char* op, double alpha) {
+  TORCH_CHECK_VALUE(std::isfinite(alpha) && alpha >= 0.0 && alpha <= (double)mnistx::AUG_MAX_ELASTIC_ALPHA, op,
+                    ": elastic_alpha must be finite with 0 <= elastic_alpha <= 64, got ", alpha);
+}
+
+void elastic_table_ok(const char* op, const Tensor& w) {
+  TORCH_CHECK_VALUE(w.device().is_cpu() && w.scalar_type() == at::kFloat && w.dim() == 1 && w.is_contiguous() &&
+                        w.numel() >= mnistx::AUG_MIN_ELASTIC_TAPS && w.numel() <= mnistx::AUG_MAX_ELASTIC_TAPS,
+                    op, ": elastic_weights must be a 1-D CPU float32 tensor of ", mnistx::AUG_MIN_ELASTIC_TAPS, " to ",
+                    mnistx::AUG_MAX_ELASTIC_TAPS, " entries (w_0 .. w_K)");
+  const float* p = w.data_ptr<float>();
+  double sum = 0.0;
+  for (int64_t k = 0; k < w.numel(); ++k) {
+    TORCH_CHECK_VALUE(std::isfinite(p[k]) && p[k] >= 0.f, op, ": elastic_weights must be finite and >= 0, got ", p[k],
+                      " at ", k);
+    sum += (k ? 2.0 : 1.0) * (double)p[k];
+  }
+  TORCH_CHECK_VALUE(std::fabs(sum - 1.0) <= 1e-5, op, ": elastic_weights must sum to 1 (w_0 + 2 sum w_k), got ", sum);
+}
+
 void augment_images(Tensor src, Tensor idx, Tensor lab_src, Tensor out, Tensor lab_out, int64_t Csrc, int64_t Cdst,
-                    int64_t pos0, int64_t seed, int64_t shift, double rotate, double scale) {
+                    int64_t pos0, int64_t seed, int64_t shift, double rotate, double scale, double elastic_alpha,
+                    optional<Tensor> elastic_weights) {
   const int64_t nb = idx.numel();
   augment_keys("augment_images", pos0, nb, seed, shift, rotate, scale);
+  elastic_alpha_ok("augment_images", elastic_alpha);
+  if (elastic_weights.has_value()) elastic_table_ok("augment_images", *elastic_weights);
+  TORCH_CHECK_VALUE(elastic_alpha == 0.0 || elastic_weights.has_value(),
+                    "augment_images: elastic_weights is required when elastic_alpha > 0");
   TORCH_CHECK((Csrc == 1 && Cdst == 1) || (Csrc == 3 && Cdst == 3) || (Csrc == 1 && Cdst == 3),
               "augment_images: (Csrc, Cdst) must be (1, 1), (3, 3) or (1, 3), got (", Csrc, ", ", Cdst, ")");
   TORCH_CHECK(src.dim() == 2 && src.size(1) == 784 * Csrc, "augment_images: src must be a [N, ", 784 * Csrc,
@@ -310,10 +337,47 @@ void augment_images(Tensor src, Tensor idx, Tensor lab_src, Tensor out, Tensor l
               "augment_images: every buffer must be on one device");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
               "augment_images: src and out must be 16-byte aligned");
+  if (elastic_alpha != 0.0) {
+    hip_ok(mnistx::augment_images_elastic(P<const uint8_t>(src), P<const int64_t>(idx), P<const int32_t>(lab_src),
+                                          (int)nb, (int)Csrc, (int)Cdst, pos0, seed, (int)shift, (float)rotate,
+                                          (float)scale, (float)elastic_alpha, elastic_weights->data_ptr<float>(),
+                                          (int)elastic_weights->numel(), out.data_ptr(),
+                                          out.scalar_type() == at::kFloat, P<int32_t>(lab_out), cur_stream()),
+           "augment_images (elastic)");
+    return;
+  }
+  // elastic_alpha = 0: the affine kernel with its arguments, whatever table came along
   hip_ok(mnistx::augment_images(P<const uint8_t>(src), P<const int64_t>(idx), P<const int32_t>(lab_src), (int)nb,
                                 (int)Csrc, (int)Cdst, pos0, seed, (int)shift, (float)rotate, (float)scale,
                                 out.data_ptr(), out.scalar_type() == at::kFloat, P<int32_t>(lab_out), cur_stream()),
          "augment_images");
+}
+
+// the 16-bit draws of the elastic fields of positions pos0 .. pos0 + n - 1 as augment_images fills
+// them: out int32 [n, 2, 784]
+void augment_elastic_draws(Tensor out, int64_t pos0, int64_t seed) {
+  TORCH_CHECK(out.dim() == 3 && out.size(1) == 2 && out.size(2) == 784,
+              "augment_elastic_draws: out must be [n, 2, 784] int32");
+  const int64_t n = out.size(0);
+  augment_keys("augment_elastic_draws", pos0, n, seed, 0, 0.0, 0.0);
+  check(out, at::kInt, n * 1568, "out");
+  TORCH_CHECK(n < ((int64_t)1 << 20), "augment_elastic_draws: n too large");
+  hip_ok(mnistx::augment_elastic_draws(P<int32_t>(out), (int)n, pos0, seed, cur_stream()), "augment_elastic_draws");
+}
+
+// the displacement field alpha * d of those positions as augment_images adds it: out fp32 [n, 2, 784]
+void augment_elastic_field(Tensor out, int64_t pos0, int64_t seed, double elastic_alpha, Tensor elastic_weights) {
+  TORCH_CHECK(out.dim() == 3 && out.size(1) == 2 && out.size(2) == 784,
+              "augment_elastic_field: out must be [n, 2, 784] fp32");
+  const int64_t n = out.size(0);
+  augment_keys("augment_elastic_field", pos0, n, seed, 0, 0.0, 0.0);
+  elastic_alpha_ok("augment_elastic_field", elastic_alpha);
+  elastic_table_ok("augment_elastic_field", elastic_weights);
+  check(out, at::kFloat, n * 1568, "out");
+  TORCH_CHECK(n < ((int64_t)1 << 20), "augment_elastic_field: n too large");
+  hip_ok(mnistx::augment_elastic_field(P<float>(out), (int)n, pos0, seed, (float)elastic_alpha,
+                                       elastic_weights.data_ptr<float>(), (int)elastic_weights.numel(), cur_stream()),
+         "augment_elastic_field");
 }
 
 // (tx, ty, theta, s) of positions pos0 .. pos0 + n - 1 as augment_images draws them: out fp32 [n, 4]
@@ -1785,7 +1849,10 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("layer"), py::arg("p"));
   m.def("augment_images", &augment_images, py::arg("src"), py::arg("idx"), py::arg("lab_src"), py::arg("out"),
         py::arg("lab_out"), py::arg("Csrc"), py::arg("Cdst"), py::arg("pos0"), py::arg("seed"), py::arg("shift"),
-        py::arg("rotate"), py::arg("scale"));
+        py::arg("rotate"), py::arg("scale"), py::arg("elastic_alpha") = 0.0, py::arg("elastic_weights") = py::none());
+  m.def("augment_elastic_draws", &augment_elastic_draws, py::arg("out"), py::arg("pos0"), py::arg("seed"));
+  m.def("augment_elastic_field", &augment_elastic_field, py::arg("out"), py::arg("pos0"), py::arg("seed"),
+        py::arg("elastic_alpha"), py::arg("elastic_weights"));
   m.def("augment_params", &augment_params, py::arg("out"), py::arg("pos0"), py::arg("seed"), py::arg("shift"),
         py::arg("rotate"), py::arg("scale"));
   m.def("fused_optimizer", &fused_optimizer, py::arg("params"), py::arg("grads"), py::arg("mom"), py::arg("ema"),

@@ -368,6 +368,22 @@ hipError_t augment_images(const uint8_t* src, const int64_t* idx, const int32_t*
 // (tx, ty, theta, s) of positions pos0 .. pos0 + n - 1 as augment_images draws them, fp32 [n, 4]
 // (what dropout_mask is to dropout: for the tests)
 hipError_t augment_params(float* out, int n, int64_t pos0, int64_t seed, int S, float R, float Z, hipStream_t st);
+// Elastic distortion (augment_elastic.hip: augment.hip's kernel text with the elastic switch set):
+// augment_images whose inverse map is displaced by alpha * (G r G^T), r the 2 x 28 x 28 field of
+// 16-bit Philox draws of (seed, pos0 + b), G the band matrix of the HOST's half table w[0 .. nw - 1]
+// (data/augment.py elastic_weights; 3 <= nw <= 25, a host pointer: the table travels as a kernel
+// argument), zero extension.  0 <= alpha <= 64: alpha = 0 is a zero field, and the binding launches
+// augment_images for it.
+constexpr float AUG_MAX_ELASTIC_ALPHA = 64.f;
+constexpr int AUG_MIN_ELASTIC_TAPS = 3, AUG_MAX_ELASTIC_TAPS = 25;
+hipError_t augment_images_elastic(const uint8_t* src, const int64_t* idx, const int32_t* lab_src, int nb, int Csrc,
+                                  int Cdst, int64_t pos0, int64_t seed, int S, float R, float Z, float alpha,
+                                  const float* w, int nw, void* out, bool out_f32, int32_t* lab_out, hipStream_t st);
+// for the tests, through the image kernel's own device functions: the draws as int32 [n, 2, 784] and
+// the displacement field alpha * d as the image kernel adds it, fp32 [n, 2, 784]
+hipError_t augment_elastic_draws(int32_t* out, int n, int64_t pos0, int64_t seed, hipStream_t st);
+hipError_t augment_elastic_field(float* out, int n, int64_t pos0, int64_t seed, float alpha, const float* w, int nw,
+                                 hipStream_t st);
 // NOTE: many splits over a small output are pre-summed IN PLACE (the slab is scratch).
 hipError_t splitk_reduce(float* slab, int splits, int M, int N, int G, int Ipad, int I, int J,
                          int bias_row, float* wdst, float* bdst, float scale, hipStream_t st);

@@ -18,6 +18,7 @@ every worker reads the whole file list in its own random order.
 """
 from __future__ import annotations
 
+import functools
 from typing import Iterator, Optional, Tuple
 
 import torch
@@ -44,18 +45,30 @@ def gather_into(ds: "DeviceDataset", idx: torch.Tensor, out_images: torch.Tensor
     out_labels[:nb].copy_(ds.labels[idx])
 
 
+@functools.lru_cache(maxsize=8)
+def _elastic_table(sigma: float) -> torch.Tensor:
+    """``aug.elastic_weights(sigma)`` as the CPU float32 tensor the binding takes, computed once."""
+    return torch.from_numpy(aug.elastic_weights(sigma).copy())
+
+
 def augment_into(ds: "DeviceDataset", idx: torch.Tensor, out_images: torch.Tensor, out_labels: torch.Tensor,
                  cfg: AugmentConfig, pos0: int) -> None:
     """``gather_into`` with the training augmentation of ``data/augment.py``: batch entry b is drawn
     from ``(cfg.seed, pos0 + b)``.  The ``augment_images`` HIP kernel on the GPU; on CPU the host
-    reference ``warp`` rounded once to the buffer's dtype."""
+    reference ``warp`` rounded once to the buffer's dtype.  With ``cfg.elastic_alpha`` non-zero both add
+    the elastic field; the kernel is handed the host's Gaussian table."""
     cdst = int(out_images.shape[-1])
     nb = idx.numel()
     if ds.device.type == "cuda":
-        kernels().augment_images(ds.images, idx, ds.labels, out_images, out_labels, ds.channels, cdst, int(pos0),
-                                 cfg.seed, cfg.shift, cfg.rotate, cfg.scale)
+        if cfg.elastic:
+            kernels().augment_images(ds.images, idx, ds.labels, out_images, out_labels, ds.channels, cdst, int(pos0),
+                                     cfg.seed, cfg.shift, cfg.rotate, cfg.scale, elastic_alpha=cfg.elastic_alpha,
+                                     elastic_weights=_elastic_table(cfg.elastic_sigma))
+        else:
+            kernels().augment_images(ds.images, idx, ds.labels, out_images, out_labels, ds.channels, cdst, int(pos0),
+                                     cfg.seed, cfg.shift, cfg.rotate, cfg.scale)
         return
-    x = aug.warp(ds.images[idx].numpy(), aug.params(cfg, pos0, nb), ds.channels, cdst)
+    x = aug.augmented(ds.images[idx].numpy(), cfg, pos0, ds.channels, cdst)
     # one rounding of the float64 value: straight to fp32, or to bf16 through fp32 rounded to odd
     x = x.astype("float32") if out_images.dtype == torch.float32 else aug.f32_round_to_odd(x)
     out_images.view(-1)[: nb * ds.hw * cdst].copy_(torch.from_numpy(x).reshape(-1))

@@ -21,7 +21,9 @@ overrides:
     getDropoutSeed(default)  -> int     (seed of the dropout masks; unset: ``default``, the run's seed)
     getAugmentShift() / getAugmentRotate() / getAugmentScale() / getAugmentSeed(default)
                              -> int / float / float / int   (training-input augmentation; 0: off)
-    getAugment(default_seed) -> AugmentConfig   (the four keys, checked)
+    getAugmentElasticAlpha() / getAugmentElasticSigma()
+                             -> float / float   (elastic distortion: displacement scale, 0: off; smoothing sigma)
+    getAugment(default_seed) -> AugmentConfig   (the six keys, checked)
 
 Defaults are the TF CIFAR-10 tutorial values that ``mnist_input.py`` mirrors
  — they are *chosen* defaults, not numbers the reference
@@ -66,6 +68,8 @@ DEFAULTS: Dict[str, Any] = {
     "augment_rotate": 0.0,       # ... random rotation about the centre of up to this many degrees (0..180); 0: off
     "augment_scale": 0.0,        # ... random zoom in [1 - z, 1 + z) (0..0.5); 0: off
     "augment_seed": None,        # seed of the counter-based augmentation draws; None: the run's seed
+    "augment_elastic_alpha": 0.0,   # ... elastic distortion: displacement scale in pixels of the smoothed field (0..64); 0: off
+    "augment_elastic_sigma": 4.0,   # ... standard deviation in pixels of the Gaussian that smooths the field (0.5..8)
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -151,7 +155,8 @@ FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", 
              "train_data", "test_data", "val_data", "beta1", "beta2", "epsilon", "rmsprop_decay",
              "adagrad_initial_accumulator", "clip_norm", "lars_eta", "lr_schedule", "warmup_steps",
              "lr_total_steps", "lr_end", "lr_power", "label_smoothing", "dropout", "dropout_seed",
-             "augment_shift", "augment_rotate", "augment_scale", "augment_seed")
+             "augment_shift", "augment_rotate", "augment_scale", "augment_seed", "augment_elastic_alpha",
+             "augment_elastic_sigma")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
@@ -303,12 +308,27 @@ def getAugmentSeed(default: int = 0) -> int:
     return check_seed(default if v is None else v, "augment_seed")
 
 
+def getAugmentElasticAlpha() -> float:
+    """The ``augment_elastic_alpha`` key: finite with 0 <= alpha <= 64, the displacement scale in pixels
+    of the smoothed random field (0: no elastic distortion)."""
+    from ..data.augment import check_elastic_alpha
+    return check_elastic_alpha(get("augment_elastic_alpha"), "augment_elastic_alpha")
+
+
+def getAugmentElasticSigma() -> float:
+    """The ``augment_elastic_sigma`` key: finite with 0.5 <= sigma <= 8, the standard deviation in pixels
+    of the smoothing Gaussian (always checked, read only when alpha > 0)."""
+    from ..data.augment import check_elastic_sigma
+    return check_elastic_sigma(get("augment_elastic_sigma"), "augment_elastic_sigma")
+
+
 def getAugment(default_seed: int = 0):
-    """The four augmentation keys as a ``data.augment.AugmentConfig`` (its ``enabled`` says whether any
+    """The six augmentation keys as a ``data.augment.AugmentConfig`` (its ``enabled`` says whether any
     amount is non-zero).  The workers augment their own inputs and the servers never see inputs, so
     parameter-server mode takes the keys as they are."""
     from ..data.augment import AugmentConfig
-    return AugmentConfig(getAugmentShift(), getAugmentRotate(), getAugmentScale(), getAugmentSeed(default_seed))
+    return AugmentConfig(getAugmentShift(), getAugmentRotate(), getAugmentScale(), getAugmentSeed(default_seed),
+                         getAugmentElasticAlpha(), getAugmentElasticSigma())
 
 
 def check_ps_dropout(job_name: str, log=print) -> None:

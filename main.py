@@ -70,6 +70,10 @@ flags.DEFINE_float("augment_scale", -1, "training images only: random zoom drawn
                    "-1: unset); any of the three on trains in --input_mode prep")
 flags.DEFINE_integer("augment_seed", -1, "seed of the augmentation draws (-1: unset, the run's --seed); a draw is a "
                      "function of (seed, stream position), so a resumed run repeats it")
+flags.DEFINE_float("augment_elastic_alpha", -1, "training images only: elastic distortion, the displacement scale in pixels "
+                   "of the smoothed random field, 0..64 (0.0: off; -1: unset); on trains in --input_mode prep")
+flags.DEFINE_float("augment_elastic_sigma", -1, "standard deviation in pixels of the Gaussian that smooths the elastic "
+                   "field, 0.5..8 (-1: unset, 4.0); read only when augment_elastic_alpha > 0")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
