@@ -59,6 +59,11 @@ def parse(argv=None):
                     help="elastic distortion: displacement scale of the smoothed random field, pixels (0..64)")
     ap.add_argument("--augment_elastic_sigma", type=float, default=4.0,
                     help="elastic distortion: standard deviation of the smoothing Gaussian, pixels (0.5..8)")
+    ap.add_argument("--mixup_alpha", type=float, default=0.0,
+                    help="mixup of the training batches, the weight from Beta(a, a) (0.1..8); the accuracy probe is an eval")
+    ap.add_argument("--cutmix_alpha", type=float, default=0.0, help="CutMix, the box area from Beta(a, a) (0.1..8)")
+    ap.add_argument("--mix_prob", type=float, default=1.0, help="probability that a batch entry is mixed at all")
+    ap.add_argument("--mix_seed", type=int, default=None, help="seed of the mixing draws (default: --seed)")
     ap.add_argument("--target", type=float, default=0.99)
     ap.add_argument("--eval_every", type=int, default=50)
     ap.add_argument("--probe", type=int, default=10000, help="training images in the accuracy probe")
@@ -112,8 +117,10 @@ def run(args) -> dict:
         opt = OptConfig(lr0=args.lr, decay_rate=0.1, decay_steps=0, momentum=0.9 if args.optimizer != "sgd" else 0.0,
                         nesterov=args.optimizer == "nesterov", use_momentum=args.optimizer != "sgd", ema_max=0.9999,
                         clip_norm=args.clip_norm, **sched)
+    from distributed_tensorflow_ibm_mnist_amd.data.mix import MixConfig
+    mix = MixConfig(args.mixup_alpha, args.cutmix_alpha, args.mix_prob, args.seed if args.mix_seed is None else args.mix_seed)
     opt = dataclasses.replace(opt, label_smoothing=args.label_smoothing, dropout=args.dropout,
-                              dropout_seed=args.seed + rank)
+                              dropout_seed=args.seed + rank, mix=mix.enabled)
     init = init_params(spec, seed=args.seed)
     if args.impl == "hip":
         from distributed_tensorflow_ibm_mnist_amd.runtime.executor import HipNet
@@ -136,9 +143,12 @@ def run(args) -> dict:
     aug = AugmentConfig(args.augment_shift, args.augment_rotate, args.augment_scale, args.seed,
                         args.augment_elastic_alpha, args.augment_elastic_sigma)
     # augmentation writes the input buffer itself: no fused gather of un-augmented rows
-    fused_in = args.impl == "hip" and args.fused_input and not aug.enabled and net.bind_u8_input(ds.images)
+    # (and so does mixing)
+    fused_in = (args.impl == "hip" and args.fused_input and not aug.enabled and not mix.enabled
+                and net.bind_u8_input(ds.images))
     loader = DeviceLoader(ds, net.x0, net.labels, rank=rank, world=world, seed=args.seed,
-                          idx_out=net.idx_buf if fused_in else None, augment=aug)
+                          idx_out=net.idx_buf if fused_in else None, augment=aug, mix=mix, out_labels2=net.labels2,
+                          out_lam=net.mix_lam)
 
     graph = None
     if args.graph and args.impl == "hip" and world == 1 and dev.type == "cuda":
@@ -198,6 +208,7 @@ def run(args) -> dict:
                    "label_smoothing": opt.label_smoothing, "dropout": opt.dropout,
                    "augment": [aug.shift, aug.rotate, aug.scale],
                    "augment_elastic": [aug.elastic_alpha, aug.elastic_sigma],
+                   "mix": [mix.mixup_alpha, mix.cutmix_alpha, mix.prob],
                    "eval_every": args.eval_every, "impl": args.impl, "hip_graph": graph is not None,
                    "parallelism": f"dp{world}"},
         "history": history[-20:],

@@ -392,6 +392,67 @@ void augment_params(Tensor out, int64_t pos0, int64_t seed, int64_t shift, doubl
          "augment_params");
 }
 
+// The tables of the mixing bindings (data/mix.py lam_table / side_table), device tensors: validated
+// for dtype, length and device (ValueError); both None is a ValueError too.
+struct MixTables {
+  const float* T = nullptr;
+  const int32_t* S = nullptr;
+};
+MixTables mix_tables(const char* op, const optional<Tensor>& lam_table, const optional<Tensor>& side_table,
+                     const Tensor& on, int64_t pos0, int64_t n, int64_t seed, int64_t thr_p) {
+  TORCH_CHECK_VALUE(pos0 >= 0 && n >= 0 && pos0 <= std::numeric_limits<int64_t>::max() - n, op,
+                    ": pos0 must be >= 0 with pos0 + n <= 2^63, got ", pos0);
+  TORCH_CHECK_VALUE(seed >= 0, op, ": seed must be >= 0 and below 2^63, got ", seed);
+  TORCH_CHECK_VALUE(thr_p >= 0 && thr_p <= 65536, op, ": thr_p must be in [0, 65536], got ", thr_p);
+  const bool ht = lam_table.has_value() && lam_table->defined(), hs = side_table.has_value() && side_table->defined();
+  TORCH_CHECK_VALUE(ht || hs, op, ": lam_table (mixup) or side_table (CutMix) is required, got neither");
+  MixTables t;
+  if (ht) {
+    TORCH_CHECK_VALUE(lam_table->scalar_type() == at::kFloat && lam_table->dim() == 1 && lam_table->numel() == 1025 &&
+                          lam_table->is_contiguous() && lam_table->device() == on.device(),
+                      op, ": lam_table must be a contiguous float32 tensor of 1025 entries on the buffer's device");
+    t.T = P<const float>(*lam_table);
+  }
+  if (hs) {
+    TORCH_CHECK_VALUE(side_table->scalar_type() == at::kInt && side_table->dim() == 1 && side_table->numel() == 1024 &&
+                          side_table->is_contiguous() && side_table->device() == on.device(),
+                      op, ": side_table must be a contiguous int32 tensor of 1024 entries on the buffer's device");
+    t.S = P<const int32_t>(*side_table);
+  }
+  return t;
+}
+
+// mixup / CutMix in place on images [>= nb, 784, cdst] bf16 (mix.hip); labels2 / lam [>= nb] receive the
+// second label and the weight of rows < nb
+void mix_images(Tensor images, Tensor labels, Tensor labels2, Tensor lam, int64_t nb, int64_t cdst, int64_t pos0,
+                int64_t seed, int64_t thr_p, optional<Tensor> lam_table, optional<Tensor> side_table) {
+  const MixTables t = mix_tables("mix_images", lam_table, side_table, images, pos0, nb, seed, thr_p);
+  TORCH_CHECK_VALUE(cdst == 1 || cdst == 3, "mix_images: cdst must be 1 or 3, got ", cdst);
+  TORCH_CHECK(nb < ((int64_t)1 << 31) / (784 * 3), "mix_images: batch too large");
+  check(images, at::kBFloat16, nb * 784 * cdst, "images");
+  check(labels, at::kInt, nb, "labels");
+  check(labels2, at::kInt, nb, "labels2");
+  check(lam, at::kFloat, nb, "lam");
+  TORCH_CHECK(labels.device() == images.device() && labels2.device() == images.device() &&
+                  lam.device() == images.device(),
+              "mix_images: every buffer must be on one device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(images.data_ptr()) % 16 == 0, "mix_images: images must be 16-byte aligned");
+  hip_ok(mnistx::mix_images(BFm(images), P<const int32_t>(labels), P<int32_t>(labels2), P<float>(lam), (int)nb,
+                            (int)cdst, pos0, seed, thr_p, t.T, t.S, cur_stream()),
+         "mix_images");
+}
+
+// what mix_images draws for positions pos0 .. pos0 + n - 1: out int32 [n, 6] = (kind, lam bits, x0, x1, y0, y1)
+void mix_params(Tensor out, int64_t pos0, int64_t seed, int64_t thr_p, optional<Tensor> lam_table,
+                optional<Tensor> side_table) {
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == 6, "mix_params: out must be [n, 6] int32");
+  const int64_t n = out.size(0);
+  const MixTables t = mix_tables("mix_params", lam_table, side_table, out, pos0, n, seed, thr_p);
+  check(out, at::kInt, n * 6, "out");
+  TORCH_CHECK(n < ((int64_t)1 << 28), "mix_params: n too large");
+  hip_ok(mnistx::mix_params(P<int32_t>(out), (int)n, pos0, seed, thr_p, t.T, t.S, cur_stream()), "mix_params");
+}
+
 void maxpool_fwd(Tensor x, Tensor y, Tensor arg, int64_t Nb, int64_t H, int64_t W, int64_t C, int64_t OH,
                  int64_t OW) {
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
@@ -469,10 +530,34 @@ float smoothing_arg(double eps, const char* op) {
   return (float)eps;
 }
 
+// labels2 / lam of the softmax-CE bindings (mixup / CutMix): both or neither (ValueError), int32 [nb]
+// and fp32 [nb] on the labels' device
+struct MixArgs {
+  const int32_t* labels2 = nullptr;
+  const float* lam = nullptr;
+};
+MixArgs mix_args(const optional<Tensor>& labels2, const optional<Tensor>& lam, int64_t nb, const Tensor* labels,
+                 const char* op) {
+  const bool h2 = labels2.has_value() && labels2->defined(), hl = lam.has_value() && lam->defined();
+  TORCH_CHECK_VALUE(h2 == hl, op, ": labels2 and lam come together, got ", h2 ? "labels2" : "lam", " alone");
+  MixArgs a;
+  if (!h2) return a;
+  TORCH_CHECK_VALUE(labels != nullptr, op, ": labels2 and lam need labels");
+  check(*labels2, at::kInt, nb, "labels2");
+  check(*lam, at::kFloat, nb, "lam");
+  TORCH_CHECK(labels2->device() == labels->device() && lam->device() == labels->device(), op,
+              ": labels2 and lam must be on the labels' device");
+  a.labels2 = P<const int32_t>(*labels2);
+  a.lam = P<const float>(*lam);
+  return a;
+}
+
 int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t B, int64_t NC, double scale,
                    optional<Tensor> dlogits, int64_t ldd, optional<Tensor> stats, optional<Tensor> probs,
-                   optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing) {
+                   optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing,
+                   optional<Tensor> labels2, optional<Tensor> lam) {
   const float eps = smoothing_arg(label_smoothing, "softmax_ce");
+  const MixArgs mx = mix_args(labels2, lam, B, labels.has_value() && labels->defined() ? &*labels : nullptr, "softmax_ce");
   TORCH_CHECK(ldl >= NC, "ldl < NC");
   check(logits, at::kFloat, B * ldl, "logits");   // whole padded rows (vector loads)
   const int32_t* lab = nullptr;
@@ -514,7 +599,7 @@ int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t 
   }
   int deferred = 0;
   hip_ok(mnistx::softmax_ce(P<const float>(logits), (int)ldl, lab, (int)B, (int)NC, (float)scale, dl, (int)ldd, st, pr,
-                            wk, cur_stream(), defer_stats ? &deferred : nullptr, db, eps),
+                            wk, cur_stream(), defer_stats ? &deferred : nullptr, db, eps, mx.labels2, mx.lam),
          "softmax_ce");
   return deferred;   // blocks whose CE partials the caller's finalize_step must combine
 }
@@ -532,8 +617,9 @@ bool ce_tail_supported(int64_t d0, int64_t nc, int64_t B) { return mnistx::ce_ta
 // the reference CNN's softmax_linear + softmax CE (+ data gradient masked by x > 0): mlp_head.hip ce_tail_k
 void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t nb, double scale, Tensor logits,
              optional<Tensor> dl, optional<Tensor> dx, Tensor stats, optional<Tensor> work, bool defer_stats,
-             optional<Tensor> dbias, double label_smoothing) {
+             optional<Tensor> dbias, double label_smoothing, optional<Tensor> labels2, optional<Tensor> lam) {
   const float eps = smoothing_arg(label_smoothing, "ce_tail");
+  const MixArgs mx = mix_args(labels2, lam, nb, &labels, "ce_tail");
   TORCH_CHECK(mnistx::ce_tail_supported(192, (int)nc, (int)std::max<int64_t>(nb, 1)), "ce_tail: unsupported geometry");
   check(x, at::kBFloat16, nb * 192, "x");
   check(w5t, at::kBFloat16, 16 * 192, "w5t");
@@ -562,9 +648,10 @@ void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t
     db = P<float>(*dbias);
   }
   TORCH_CHECK(eps == 0.f || pdl != nullptr, "ce_tail: label_smoothing is a training quantity and needs dl");
+  TORCH_CHECK(mx.labels2 == nullptr || pdl != nullptr, "ce_tail: labels2 / lam are training quantities and need dl");
   hip_ok(mnistx::ce_tail(BF(x), BF(w5t), P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale,
                          P<float>(logits), pdl, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr, cur_stream(),
-                         defer_stats ? 1 : 0, db, eps),
+                         defer_stats ? 1 : 0, db, eps, mx.labels2, mx.lam),
          "ce_tail");
 }
 
@@ -594,8 +681,10 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
               int64_t nc, Tensor labels, int64_t nb, double scale, Tensor h3, Tensor h4, Tensor logits,
               optional<Tensor> dl, optional<Tensor> dh4, optional<Tensor> dh3, optional<Tensor> dx, Tensor stats,
               optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing, double dropout,
-              optional<Tensor> drop_step, int64_t drop_seed, int64_t drop_layer3, int64_t drop_layer4) {
+              optional<Tensor> drop_step, int64_t drop_seed, int64_t drop_layer3, int64_t drop_layer4,
+              optional<Tensor> labels2, optional<Tensor> lam) {
   const float eps = smoothing_arg(label_smoothing, "mlp_head");
+  const MixArgs mx = mix_args(labels2, lam, nb, &labels, "mlp_head");
   const DropArgs da = dropout_rate(dropout, "mlp_head");
   mnistx::HeadDrop hd{};
   if (dropout != 0.0) {   // 0 launches what is launched without the key
@@ -648,10 +737,12 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
   }
   TORCH_CHECK(eps == 0.f || pdl != nullptr, "mlp_head: label_smoothing is a training quantity and needs dl");
   TORCH_CHECK(hd.step == nullptr || pdl != nullptr, "mlp_head: dropout is a training quantity and needs dl");
+  TORCH_CHECK(mx.labels2 == nullptr || pdl != nullptr, "mlp_head: labels2 / lam are training quantities and need dl");
   hip_ok(mnistx::mlp_head(BF(x), BF(w3t), P<const float>(b3), (int)n1, BF(w4t), P<const float>(b4), (int)n2, BF(w5t),
                           P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale, BFm(h3),
                           BFm(h4), P<float>(logits), pdl, pdh4, pdh3, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr,
-                          cur_stream(), (defer_stats && has_work) ? 1 : 0, db, eps, hd.step ? &hd : nullptr),
+                          cur_stream(), (defer_stats && has_work) ? 1 : 0, db, eps, hd.step ? &hd : nullptr, mx.labels2,
+                          mx.lam),
          "mlp_head");
 }
 
@@ -1822,7 +1913,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("softmax_ce", &softmax_ce, py::arg("logits"), py::arg("ldl"), py::arg("labels"), py::arg("B"), py::arg("NC"),
         py::arg("scale"), py::arg("dlogits"), py::arg("ldd"), py::arg("stats"), py::arg("probs"),
         py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
-        py::arg("label_smoothing") = 0.0);
+        py::arg("label_smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none());
   m.def("softmax_ce_dbias_blocks",
         [](int64_t B, int64_t ldl) { return (int64_t)mnistx::softmax_ce_dbias_blocks((int)B, (int)ldl); });
   m.def("splitk_reduce", &splitk_reduce);
@@ -1833,14 +1924,15 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("ce_tail", &ce_tail, py::arg("x"), py::arg("w5t"), py::arg("b5"), py::arg("nc"), py::arg("labels"),
         py::arg("nb"), py::arg("scale"), py::arg("logits"), py::arg("dl") = py::none(), py::arg("dx") = py::none(),
         py::arg("stats"), py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
-        py::arg("label_smoothing") = 0.0);
+        py::arg("label_smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none());
   m.def("mlp_head", &mlp_head, py::arg("x"), py::arg("w3t"), py::arg("b3"), py::arg("n1"), py::arg("w4t"),
         py::arg("b4"), py::arg("n2"), py::arg("w5t"), py::arg("b5"), py::arg("nc"), py::arg("labels"), py::arg("nb"),
         py::arg("scale"), py::arg("h3"), py::arg("h4"), py::arg("logits"), py::arg("dl") = py::none(),
         py::arg("dh4") = py::none(), py::arg("dh3") = py::none(), py::arg("dx") = py::none(), py::arg("stats"),
         py::arg("work"), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
         py::arg("label_smoothing") = 0.0, py::arg("dropout") = 0.0, py::arg("drop_step") = py::none(),
-        py::arg("drop_seed") = 0, py::arg("drop_layer3") = 0, py::arg("drop_layer4") = 0);
+        py::arg("drop_seed") = 0, py::arg("drop_layer3") = 0, py::arg("drop_layer4") = 0,
+        py::arg("labels2") = py::none(), py::arg("lam") = py::none());
   m.def("dropout_fwd", &dropout_fwd, py::arg("x"), py::arg("nb"), py::arg("n"), py::arg("ld"), py::arg("step"),
         py::arg("seed"), py::arg("layer"), py::arg("p"));
   m.def("dropout_bwd", &dropout_bwd, py::arg("dy"), py::arg("nb"), py::arg("n"), py::arg("ld"), py::arg("step"),
@@ -1853,6 +1945,11 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("augment_elastic_draws", &augment_elastic_draws, py::arg("out"), py::arg("pos0"), py::arg("seed"));
   m.def("augment_elastic_field", &augment_elastic_field, py::arg("out"), py::arg("pos0"), py::arg("seed"),
         py::arg("elastic_alpha"), py::arg("elastic_weights"));
+  m.def("mix_images", &mix_images, py::arg("images"), py::arg("labels"), py::arg("labels2"), py::arg("lam"),
+        py::arg("nb"), py::arg("cdst"), py::arg("pos0"), py::arg("seed"), py::arg("thr_p"),
+        py::arg("lam_table") = py::none(), py::arg("side_table") = py::none());
+  m.def("mix_params", &mix_params, py::arg("out"), py::arg("pos0"), py::arg("seed"), py::arg("thr_p"),
+        py::arg("lam_table") = py::none(), py::arg("side_table") = py::none());
   m.def("augment_params", &augment_params, py::arg("out"), py::arg("pos0"), py::arg("seed"), py::arg("shift"),
         py::arg("rotate"), py::arg("scale"));
   m.def("fused_optimizer", &fused_optimizer, py::arg("params"), py::arg("grads"), py::arg("mom"), py::arg("ema"),

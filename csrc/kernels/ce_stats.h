@@ -7,6 +7,8 @@
 #pragma once
 #include "common.h"
 
+#include <type_traits>
+
 constexpr int CE_MAXB = 1024;  // max blocks per launch (work holds 4 floats per block + ticket)
 
 // Label smoothing.  The softmax-CE kernels take a compile-time SMOOTH switch; the smoothed
@@ -21,6 +23,43 @@ DEV float smooth_eps(T... eps) {
   static_assert(sizeof...(T) <= 1, "one eps at most");
   if constexpr (sizeof...(T) == 0) return 0.f;
   else return (eps + ...);
+}
+
+// Two labels per row (mixup / CutMix, mix.hip).  The MIX form of the same kernels is read off the
+// pack's types: (eps, const int32_t* labels2, const float* lam [, ...]) instead of (eps); eps is
+// always there and may be 0, so mixing and smoothing share one instantiation per kernel.  With
+// ya = labels[m], yb = labels2[m], lam = lam[m] and om = 1 - lam:
+//   loss = log(se) - on * (lam (l_ya - mx) + om (l_yb - mx)) - off * sum_{c < NC} (l_c - mx)
+//   dl_c = (p_c - on * (lam [c == ya] + om [c == yb]) - off) * scale
+// A row with lam == 1 drops the yb term by a select (mix_om, mix_logit), never by a product with 0:
+// an infinite l_yb leaves such a row finite.  lam + om is exactly 1 for lam in [0.5, 1], so ya == yb
+// gives `on` at that class.  The top-1 count stays l_ya >= mx: ya is the dominant label.
+template <typename... T>
+constexpr bool pack_has_mix = (std::is_same_v<T, const float*> || ...);
+template <typename... R>
+DEV float mix_eps(float e, const int32_t*, const float*, R...) { return e; }
+template <typename... R>
+DEV const int32_t* mix_labels2(float, const int32_t* l2, const float*, R...) { return l2; }
+template <typename... R>
+DEV const float* mix_lam(float, const int32_t*, const float* lm, R...) { return lm; }
+// labels2[m] / lam[m]; the fused heads pass min(m, nb - 1), as their X loads do (a row past the batch
+// is never stored or counted), so the loads sit under no branch and repeated calls merge into one
+template <typename... A>
+DEV int mix_row_label(int64_t m, A... a) { return mix_labels2(a...)[m]; }
+template <typename... A>
+DEV float mix_row_lam(int64_t m, A... a) { return mix_lam(a...)[m]; }
+DEV float mix_om(float lam) { return lam < 1.f ? 1.f - lam : 0.f; }
+// lam (l_ya - mx) + om (l_yb - mx) from da = l_ya - mx, db = l_yb - mx
+DEV float mix_logit(float lam, float da, float db) { return lam < 1.f ? fmaf(lam, da, (1.f - lam) * db) : da; }
+// the loss from tl = mix_logit(..), the class sum sd and lse = log(se).  eps = 0 (off == 0) leaves the
+// class sum out by a select: a -inf logit in a class no label names makes sd -inf, and 0 * inf is NaN
+DEV float mix_ce(float on, float off, float tl, float sd, float lse) {
+  const float a = fmaf(-on, tl, lse);
+  return off != 0.f ? fmaf(-off, sd, a) : a;
+}
+// the target of class c: on * (lam [c == ya] + om [c == yb]) + off
+DEV float mix_target(int c, int ya, int yb, float lam, float om, float on, float off) {
+  return fmaf(on, (c == ya ? lam : 0.f) + (c == yb ? om : 0.f), off);
 }
 
 // Every thread of the block must call this (it synchronises the block).

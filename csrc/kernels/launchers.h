@@ -288,12 +288,16 @@ hipError_t lrn_pool_bwd(const bf16_t* x, const bf16_t* dP, const uint8_t* arg, i
 // caller's finalize_step combines them (ce_stats.h defer)
 // dbias (optional, with dlogits): per-block fp32 column sums of dlogits [blocks][ldl]
 // (blocks = softmax_ce_dbias_blocks; only the row kernel, ldl 16 / 32, writes them)
+// labels2 / lam (here and on mlp_head, ce_tail; both or neither): a second label and the weight of the
+// first per row, the target lam * q(labels) + (1 - lam) * q(labels2) of mixup / CutMix (ce_stats.h,
+// mix.hip); they launch the mixed instantiation, which takes label_smoothing as it is, 0 included
 // label_smoothing (here and on f32_softmax_ce, mlp_head, ce_tail): eps of the smoothed target
 // (1 - eps) * onehot + eps / NC (ce_stats.h).  0 launches the plain instantiation with the plain
 // arguments; any other value the smoothed one (needs labels; the fused heads: the training form)
 hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale,
                       bf16_t* dlogits, int ldd, float* stats, float* probs, float* work, hipStream_t st,
-                      int* defer_blocks = nullptr, float* dbias = nullptr, float label_smoothing = 0.f);
+                      int* defer_blocks = nullptr, float* dbias = nullptr, float label_smoothing = 0.f,
+                      const int32_t* labels2 = nullptr, const float* lam = nullptr);
 int softmax_ce_dbias_blocks(int B, int ldl);
 // Fused LeNet-5 dense head (mlp_head.hip): fc3/fc4/fc5 + softmax-CE (+ with dl:
 // the data-gradient chain dlogits -> dh4 -> dh3 -> dx).  Writes h3, h4, logits
@@ -316,7 +320,8 @@ hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1,
                     int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
                     bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
                     float* stats, float* work, hipStream_t st, int defer_stats = 0, float* dbias = nullptr,
-                    float label_smoothing = 0.f, const HeadDrop* drop = nullptr);
+                    float label_smoothing = 0.f, const HeadDrop* drop = nullptr, const int32_t* labels2 = nullptr,
+                    const float* lam = nullptr);
 // blocks of one mlp_head launch (its per-block CE partials when defer_stats is set)
 int mlp_head_blocks(int nb);
 // the reference CNN's softmax_linear (192 -> nc <= 16) + softmax CE + its data gradient (masked by
@@ -326,7 +331,8 @@ bool ce_tail_supported(int d0, int nc, int B);
 int ce_tail_blocks(int nb);
 hipError_t ce_tail(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
                    float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                   int defer_stats, float* dbias, float label_smoothing = 0.f);
+                   int defer_stats, float* dbias, float label_smoothing = 0.f, const int32_t* labels2 = nullptr,
+                   const float* lam = nullptr);
 // the smoothed instantiations (mlp_head_smooth.hip), which mlp_head / ce_tail call for
 // label_smoothing != 0: the gradient form only (dl required)
 int ce_tail_nw(int nb);
@@ -344,6 +350,18 @@ hipError_t mlp_head_drop(const bf16_t* x, const bf16_t* w3t, const float* b3, in
                          int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
                          bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
                          float* dbias, float label_smoothing, const HeadDrop& drop);
+// the two-label instantiations (mlp_head_mix.hip; mixup / CutMix), which mlp_head / ce_tail call when
+// labels2 and lam are given: the gradient form only; label_smoothing as it is (0 allowed); drop may be
+// nullptr
+hipError_t ce_tail_mix(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
+                       float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
+                       int defer_stats, float* dbias, float label_smoothing, const int32_t* labels2, const float* lam);
+hipError_t mlp_head_mix(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
+                        const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
+                        int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
+                        bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
+                        float* dbias, float label_smoothing, const int32_t* labels2, const float* lam,
+                        const HeadDrop* drop);
 // Stand-alone dropout (dropout.hip) on a [nb, ld] bf16 buffer with n <= ld real columns, in place:
 // x = keep ? bf16(x * inv_keep) : +0, the keep bits of (seed, *step, layer) from dropout_rng.h.
 // Forward (on the activation) and backward (on the gradient: the bits are recomputed) are the same
@@ -384,6 +402,19 @@ hipError_t augment_images_elastic(const uint8_t* src, const int64_t* idx, const 
 hipError_t augment_elastic_draws(int32_t* out, int n, int64_t pos0, int64_t seed, hipStream_t st);
 hipError_t augment_elastic_field(float* out, int n, int64_t pos0, int64_t seed, float alpha, const float* w, int nw,
                                  hipStream_t st);
+// Mixup and CutMix (mix.hip), in place on images [nb, 784, C] bf16 (C 1 or 3, 16-byte aligned): entry b is
+// mixed with entry nb - 1 - b as (seed, pos0 + b) draws it; labels2 [nb] and lam [nb] receive the second
+// label and the weight of every row (an unmixed entry: its own label and 1; its bytes are not
+// touched).  T: the host's 1025 fp32 quantiles of the mixup weight (data/mix.py lam_table), S: its
+// 1024 int32 CutMix box sides (side_table), both DEVICE pointers; nullptr turns that form off, both
+// nullptr is invalid.  thr_p: an entry is mixed when the high 16 bits of its first word are below it
+// (0 .. 65536).
+hipError_t mix_images(bf16_t* images, const int32_t* labels, int32_t* labels2, float* lam, int nb, int C, int64_t pos0,
+                      int64_t seed, int64_t thr_p, const float* T, const int32_t* S, hipStream_t st);
+// what mix_images draws for positions pos0 .. pos0 + n - 1, through its own device function: int32
+// [n, 6] = (0 unmixed / 1 mixup / 2 CutMix, the bits of lam, x0, x1, y0, y1); for the tests
+hipError_t mix_params(int32_t* out, int n, int64_t pos0, int64_t seed, int64_t thr_p, const float* T, const int32_t* S,
+                      hipStream_t st);
 // NOTE: many splits over a small output are pre-summed IN PLACE (the slab is scratch).
 hipError_t splitk_reduce(float* slab, int splits, int M, int N, int G, int Ipad, int I, int J,
                          int bias_row, float* wdst, float* bdst, float scale, hipStream_t st);

@@ -527,13 +527,19 @@ __global__ __launch_bounds__(TPB) void lrn_pool14_bwd_k(const bf16_t* __restrict
 // ------------------------------------------------------------------ K8 softmax cross-entropy
 // stats[0] += sum(-log p[label]) ; stats[1] += #(logit[label] == max) ; stats[2] = 1 if non-finite.
 // SMOOTH: label smoothing (ce_stats.h), eps as the one member of the trailing argument pack.
+// MIX (the pack is eps, labels2, lam): two labels and a weight per row (ce_stats.h).
 template <bool SMOOTH = false, typename... EPS>
 __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ labels, int B,
                              int NC, float scale, bf16_t* __restrict__ dl, int ldd, float* __restrict__ stats,
                              float* __restrict__ probs, EPS... eps) {
-  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
+  constexpr bool MIX = pack_has_mix<EPS...>;
+  static_assert(sizeof...(EPS) == (MIX ? 3 : SMOOTH ? 1 : 0) && (SMOOTH || !MIX),
+                "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
   float sm_on = 1.f, sm_off = 0.f;
-  if constexpr (SMOOTH) {
+  if constexpr (MIX) {
+    sm_on = 1.f - mix_eps(eps...);
+    sm_off = mix_eps(eps...) / (float)NC;
+  } else if constexpr (SMOOTH) {
     sm_on = 1.f - smooth_eps(eps...);
     sm_off = smooth_eps(eps...) / (float)NC;
   }
@@ -550,7 +556,13 @@ __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const in
     const int lab = labels ? labels[row] : -1;
     if (labels) {
       const float ll = l[lab];
-      if constexpr (SMOOTH) {
+      if constexpr (MIX) {
+        const int lab2 = mix_labels2(eps...)[row];
+        const float lm = mix_lam(eps...)[row];
+        float sd = 0.f;
+        for (int c = 0; c < NC; ++c) sd += l[c] - mx;
+        loss = mix_ce(sm_on, sm_off, mix_logit(lm, ll - mx, l[lab2] - mx), sd, __logf(se));
+      } else if constexpr (SMOOTH) {
         float sd = 0.f;
         for (int c = 0; c < NC; ++c) sd += l[c] - mx;
         loss = fmaf(-sm_off, sd, fmaf(-sm_on, ll - mx, __logf(se)));
@@ -564,7 +576,11 @@ __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const in
       bf16_t* d = dl + (int64_t)row * ldd;
       for (int c = 0; c < ldd; ++c) {
         float g = 0.f;
-        if constexpr (SMOOTH) {
+        if constexpr (MIX) {
+          const int lab2 = mix_labels2(eps...)[row];
+          const float lm = mix_lam(eps...)[row];
+          if (c < NC) g = (__expf(l[c] - mx) * inv - mix_target(c, lab, lab2, lm, mix_om(lm), sm_on, sm_off)) * scale;
+        } else if constexpr (SMOOTH) {
           if (c < NC) g = (__expf(l[c] - mx) * inv - (c == lab ? sm_on + sm_off : sm_off)) * scale;
         } else {
           if (c < NC) g = (__expf(l[c] - mx) * inv - (c == lab ? 1.f : 0.f)) * scale;
@@ -599,9 +615,14 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
                                                          float* __restrict__ stats, float* __restrict__ probs,
                                                          float* __restrict__ work, int defer_stats,
                                                          float* __restrict__ dbias, EPS... eps) {
-  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
+  constexpr bool MIX = pack_has_mix<EPS...>;
+  static_assert(sizeof...(EPS) == (MIX ? 3 : SMOOTH ? 1 : 0) && (SMOOTH || !MIX),
+                "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
   float sm_on = 1.f, sm_off = 0.f;
-  if constexpr (SMOOTH) {
+  if constexpr (MIX) {
+    sm_on = 1.f - mix_eps(eps...);
+    sm_off = mix_eps(eps...) / (float)NC;
+  } else if constexpr (SMOOTH) {
     sm_on = 1.f - smooth_eps(eps...);
     sm_off = smooth_eps(eps...) / (float)NC;
   }
@@ -636,7 +657,17 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
 #pragma unroll
       for (int c = 0; c < LD; ++c) ll = (c == lab) ? l[c] : ll;
       float lo;
-      if constexpr (SMOOTH) {
+      if constexpr (MIX) {
+        const int lab2 = mix_labels2(eps...)[row];
+        const float lm = mix_lam(eps...)[row];
+        float lb = 0.f, sd = 0.f;
+#pragma unroll
+        for (int c = 0; c < LD; ++c) lb = (c == lab2) ? l[c] : lb;
+#pragma unroll
+        for (int c = 0; c < LD; ++c)
+          if (c < NC) sd += l[c] - mx;
+        lo = mix_ce(sm_on, sm_off, mix_logit(lm, ll - mx, lb - mx), sd, __logf(se));
+      } else if constexpr (SMOOTH) {
         float sd = 0.f;
 #pragma unroll
         for (int c = 0; c < LD; ++c)
@@ -657,7 +688,12 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
         for (int h = 0; h < 4; ++h) {
           const int c0 = 8 * v + 2 * h;
           float g0, g1;
-          if constexpr (SMOOTH) {
+          if constexpr (MIX) {
+            const int lab2 = mix_labels2(eps...)[row];   // (the loads of the loss above: merged by the compiler)
+            const float lm = mix_lam(eps...)[row], om = mix_om(lm);
+            g0 = c0 < NC ? (e[c0] * inv - mix_target(c0, lab, lab2, lm, om, sm_on, sm_off)) * scale : 0.f;
+            g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - mix_target(c0 + 1, lab, lab2, lm, om, sm_on, sm_off)) * scale : 0.f;
+          } else if constexpr (SMOOTH) {
             g0 = c0 < NC ? (e[c0] * inv - (c0 == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
             g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - (c0 + 1 == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
           } else {
@@ -1738,8 +1774,11 @@ int softmax_ce_dbias_blocks(int B, int ldl) {
 
 hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale,
                       bf16_t* dlogits, int ldd, float* stats, float* probs, float* work, hipStream_t st,
-                      int* defer_blocks, float* dbias, float label_smoothing) {
+                      int* defer_blocks, float* dbias, float label_smoothing, const int32_t* labels2,
+                      const float* lam) {
   const int nb = (int)std::min<int64_t>(CE_MAXB, ((int64_t)B + 255) / 256);
+  const bool mix = labels2 != nullptr;   // the mixed instantiations: eps (0 allowed), labels2, lam
+  if (mix != (lam != nullptr) || (mix && !labels)) return hipErrorInvalidValue;
   const bool smooth = label_smoothing != 0.f;   // the smoothed instantiations, eps as their last argument
   if (smooth && !labels) return hipErrorInvalidValue;
   if (defer_blocks) *defer_blocks = 0;
@@ -1748,7 +1787,15 @@ hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B
   if (rows_ok && B > 0) {
     const int defer = (defer_blocks && work && stats) ? 1 : 0;
     if (defer) *defer_blocks = nb;
-    if (smooth && ldl == 16)
+    if (mix && ldl == 16)
+      hipLaunchKernelGGL((softmax_ce_rows_k<16, true, float, const int32_t*, const float*>), dim3(nb), dim3(256), 0, st,
+                         logits, labels, B, NC, scale, dlogits, stats, probs, work, defer, dbias, label_smoothing,
+                         labels2, lam);
+    else if (mix)
+      hipLaunchKernelGGL((softmax_ce_rows_k<32, true, float, const int32_t*, const float*>), dim3(nb), dim3(256), 0, st,
+                         logits, labels, B, NC, scale, dlogits, stats, probs, work, defer, dbias, label_smoothing,
+                         labels2, lam);
+    else if (smooth && ldl == 16)
       hipLaunchKernelGGL((softmax_ce_rows_k<16, true, float>), dim3(nb), dim3(256), 0, st, logits, labels, B, NC, scale,
                          dlogits, stats, probs, work, defer, dbias, label_smoothing);
     else if (smooth)
@@ -1763,7 +1810,10 @@ hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B
     return hipGetLastError();
   }
   if (dbias) return hipErrorInvalidValue;   // the row kernel's block partials only
-  if (smooth)
+  if (mix)
+    hipLaunchKernelGGL((softmax_ce_k<true, float, const int32_t*, const float*>), dim3((B + TPB - 1) / TPB), dim3(TPB), 0,
+                       st, logits, ldl, labels, B, NC, scale, dlogits, ldd, stats, probs, label_smoothing, labels2, lam);
+  else if (smooth)
     hipLaunchKernelGGL((softmax_ce_k<true, float>), dim3((B + TPB - 1) / TPB), dim3(TPB), 0, st, logits, ldl, labels, B,
                        NC, scale, dlogits, ldd, stats, probs, label_smoothing);
   else

@@ -179,7 +179,20 @@ DEV float smooth_loss(const float (&lg)[8], float mx, float se, float ll, int h,
   return fmaf(-off, sd, fmaf(-on, ll - mx, __logf(se)));
 }
 
-// The trailing argument pack of mlp_head_k: eps (SMOOTH) first, then the dropout arguments.  DROP is
+// The two-label loss of such a row (MIX, ce_stats.h): smooth_loss with lam (l_ya - mx) + om (l_yb - mx)
+// in place of l_y - mx; lb is l_yb, found and joined as ll is.  Both lanes of a row must call it.
+DEV float mix_loss(const float (&lg)[8], float mx, float se, float ll, float lb, float lam, int h, int nc, float eps) {
+  const float off = eps / (float)nc, on = 1.f - eps;
+  float sd = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    if ((i & 3) + 8 * (i >> 2) + 4 * h < nc) sd += lg[i] - mx;
+  sd += __shfl_xor(sd, 32, 64);
+  return mix_ce(on, off, mix_logit(lam, ll - mx, lb - mx), sd, __logf(se));
+}
+
+// The trailing argument pack of mlp_head_k: eps (SMOOTH) first, then labels2 and lam (MIX, which
+// always comes with eps), then the dropout arguments.  DROP is
 // read off the pack's types instead of being one more template argument, so the plain and the
 // smoothed instantiation keep the names (and the code objects) they had before dropout existed.
 template <typename... A>
@@ -188,6 +201,9 @@ DEV float pack_eps(float e) { return e; }
 DEV float pack_eps(float e, const HeadDrop&) { return e; }
 DEV const HeadDrop& pack_drop(const HeadDrop& d) { return d; }
 DEV const HeadDrop& pack_drop(float, const HeadDrop& d) { return d; }
+DEV float pack_eps(float e, const int32_t*, const float*) { return e; }
+DEV float pack_eps(float e, const int32_t*, const float*, const HeadDrop&) { return e; }
+DEV const HeadDrop& pack_drop(float, const int32_t*, const float*, const HeadDrop& d) { return d; }
 
 // The draws of features 8g + 4h .. + 3 (registers 4q .. 4q + 3 of a tile, draw group g = 4 tile + q)
 // of batch row m: words 2h and 2h + 1 of group g's Philox call.  The two half-row lanes need every
@@ -219,6 +235,8 @@ DEV void drop_pack(const DropKey& k, float inv_keep, uint32_t m, uint32_t g, int
 // loads under the current tile's backward chain) measured slower (0.540 vs 0.53 ms/step,
 // profiles/r3/lenet/knobs/).
 // SMOOTH: label smoothing (ce_stats.h), eps as the first member of the trailing argument pack.
+// MIX (labels2 and lam behind eps; gradient form only): two labels and a weight per row (ce_stats.h).
+// l_yb is found as l_ya is, one more select chain and one more __shfl_xor; 8 more bytes read per row.
 // DROP (a HeadDrop closes the pack; gradient form only): dropout on h3 and h4 (dropout_rng.h).  The
 // masks are drawn where the activations are packed; h3 / h4 are stored dropped and scaled, so the
 // weight and bias gradients need nothing; the backward reads the bit off the packed activation
@@ -235,9 +253,11 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
                                                   bf16_t* __restrict__ dx, float* __restrict__ stats,
                                                   float* __restrict__ work, int defer_stats,
                                                   float* __restrict__ dbias, EPS... eps) {
-  constexpr bool DROP = pack_has_drop<EPS...>;
-  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0) + (DROP ? 1 : 0), "the pack is [eps] [HeadDrop]");
+  constexpr bool DROP = pack_has_drop<EPS...>, MIX = pack_has_mix<EPS...>;
+  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0) + (MIX ? 2 : 0) + (DROP ? 1 : 0),
+                "the pack is [eps] [labels2, lam] [HeadDrop]");
   static_assert(GRADS || !DROP, "dropout is a training quantity: the gradient form only");
+  static_assert(!MIX || (SMOOTH && GRADS), "the mixed form takes eps and is the gradient form only");
   __shared__ __attribute__((aligned(16))) bf16_t i3[R3 * S3];
   __shared__ __attribute__((aligned(16))) bf16_t i4[R4 * S4];
   __shared__ __attribute__((aligned(16))) bf16_t i5[R5 * S5];
@@ -411,7 +431,20 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) ll = ((i & 3) + 8 * (i >> 2) + 4 * h == lab) ? lg[i] : ll;
     ll += __shfl_xor(ll, 32, 64);
-    if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
+    if constexpr (MIX) {
+      const int lab2 = mix_row_label(min(m, nb - 1), eps...);
+      const float lm = mix_row_lam(min(m, nb - 1), eps...);
+      float lb = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) lb = ((i & 3) + 8 * (i >> 2) + 4 * h == lab2) ? lg[i] : lb;
+      lb += __shfl_xor(lb, 32, 64);
+      const float lo = mix_loss(lg, mx, se, ll, lb, lm, h, nc, mix_eps(eps...));   // by both half-rows
+      if (valid && h == 0) {
+        loss += lo;
+        corr += (ll >= mx) ? 1.f : 0.f;
+        bad = isfinite(lo) ? bad : 1.f;
+      }
+    } else if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
       const float lo = smooth_loss(lg, mx, se, ll, h, nc, pack_eps(eps...));   // by both half-rows
       if (valid && h == 0) {
         loss += lo;
@@ -433,7 +466,12 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int i = 2 * w + k, cls = (i & 3) + 8 * (i >> 2) + 4 * h;
-          if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
+          if constexpr (MIX) {      // q_c = (1 - eps) (lam [c == ya] + om [c == yb]) + eps / nc
+            const float off = mix_eps(eps...) / (float)nc, on = 1.f - mix_eps(eps...);
+            const int lab2 = mix_row_label(min(m, nb - 1), eps...);   // (the loads of the loss above: merged by the compiler)
+            const float lm = mix_row_lam(min(m, nb - 1), eps...);
+            g2[k] = cls < nc ? (e[i] * inv - mix_target(cls, lab, lab2, lm, mix_om(lm), on, off)) * scale : 0.f;
+          } else if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
             const float off = pack_eps(eps...) / (float)nc, on = 1.f - pack_eps(eps...);
             g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? on + off : off)) * scale : 0.f;
           } else {
@@ -565,7 +603,9 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
                                                      bf16_t* __restrict__ dx, float* __restrict__ stats,
                                                      float* __restrict__ work, int defer_stats,
                                                      float* __restrict__ dbias, EPS... eps) {
-  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
+  constexpr bool MIX = pack_has_mix<EPS...>;
+  static_assert(sizeof...(EPS) == (MIX ? 3 : SMOOTH ? 1 : 0) && (!MIX || (SMOOTH && GRADS)),
+                "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
   __shared__ __attribute__((aligned(16))) bf16_t i5[16 * TD0];
   __shared__ __attribute__((aligned(16))) float bias5[LD3];
   __shared__ __attribute__((aligned(16))) bf16_t stage[TNW * STG];
@@ -632,7 +672,20 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) ll = ((i & 3) + 8 * (i >> 2) + 4 * h == lab) ? lg[i] : ll;
     ll += __shfl_xor(ll, 32, 64);
-    if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
+    if constexpr (MIX) {
+      const int lab2 = mix_row_label(min(m, nb - 1), eps...);
+      const float lm = mix_row_lam(min(m, nb - 1), eps...);
+      float lb = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) lb = ((i & 3) + 8 * (i >> 2) + 4 * h == lab2) ? lg[i] : lb;
+      lb += __shfl_xor(lb, 32, 64);
+      const float lo = mix_loss(lg, mx, se, ll, lb, lm, h, nc, mix_eps(eps...));   // by both half-rows
+      if (valid && h == 0) {
+        loss += lo;
+        corr += (ll >= mx) ? 1.f : 0.f;
+        bad = isfinite(lo) ? bad : 1.f;
+      }
+    } else if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
       const float lo = smooth_loss(lg, mx, se, ll, h, nc, smooth_eps(eps...));   // by both half-rows
       if (valid && h == 0) {
         loss += lo;
@@ -654,7 +707,12 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int i = 2 * w + k, cls = (i & 3) + 8 * (i >> 2) + 4 * h;
-          if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
+          if constexpr (MIX) {      // q_c = (1 - eps) (lam [c == ya] + om [c == yb]) + eps / nc
+            const float off = mix_eps(eps...) / (float)nc, on = 1.f - mix_eps(eps...);
+            const int lab2 = mix_row_label(min(m, nb - 1), eps...);   // (the loads of the loss above: merged by the compiler)
+            const float lm = mix_row_lam(min(m, nb - 1), eps...);
+            g2[k] = cls < nc ? (e[i] * inv - mix_target(cls, lab, lab2, lm, mix_om(lm), on, off)) * scale : 0.f;
+          } else if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
             const float off = smooth_eps(eps...) / (float)nc, on = 1.f - smooth_eps(eps...);
             g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? on + off : off)) * scale : 0.f;
           } else {
@@ -768,6 +826,45 @@ hipError_t mlp_head_drop(const bf16_t* x, const bf16_t* w3t, const float* b3, in
                        dbias, drop);
   return hipGetLastError();
 }
+#elif defined(MNISTX_HEAD_MIX_TU)
+// mlp_head_mix.hip: the two-label instantiations (mixup / CutMix; eps always in the pack, 0 allowed)
+// of both fused heads, with dropout and without, a translation unit of their own for the same reason.
+hipError_t ce_tail_mix(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
+                       float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
+                       int defer_stats, float* dbias, float label_smoothing, const int32_t* labels2, const float* lam) {
+  if (nb <= 0) return hipSuccess;
+  if (!dl || !labels2 || !lam) return hipErrorInvalidValue;   // a training quantity: the gradient form only
+  const dim3 grid(ce_tail_blocks(nb));
+  const int nw = ce_tail_nw(nb);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(64 * nw), 0, st, x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats,
+                       work, defer_stats, dbias, label_smoothing, labels2, lam);
+  };
+  if (nw == 1) go(ce_tail_k<1, true, true, float, const int32_t*, const float*>);
+  else if (nw == 2) go(ce_tail_k<2, true, true, float, const int32_t*, const float*>);
+  else go(ce_tail_k<4, true, true, float, const int32_t*, const float*>);
+  return hipGetLastError();
+}
+
+hipError_t mlp_head_mix(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
+                        const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
+                        int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
+                        bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
+                        float* dbias, float label_smoothing, const int32_t* labels2, const float* lam,
+                        const HeadDrop* drop) {
+  if (nb <= 0) return hipSuccess;
+  if (!dl || !labels2 || !lam || (drop && !drop->step)) return hipErrorInvalidValue;
+  const dim3 grid((nb + ROWS - 1) / ROWS);
+  if (drop)
+    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float, const int32_t*, const float*, HeadDrop>), grid,
+                       dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits,
+                       dl, dh4, dh3, dx, stats, work, defer_stats, dbias, label_smoothing, labels2, lam, *drop);
+  else
+    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float, const int32_t*, const float*>), grid, dim3(NTH), 0, st,
+                       x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx,
+                       stats, work, defer_stats, dbias, label_smoothing, labels2, lam);
+  return hipGetLastError();
+}
 #else
 // waves per block (32 rows each): 2, or more when the block count would exceed the CE partial
 // slots; MNISTX_CE_TAIL_NW overrides (1, 2 or 4).  At B = 16384 2 waves (256 blocks) measured
@@ -787,7 +884,11 @@ bool ce_tail_supported(int d0, int nc, int B) { return d0 == TD0 && nc > 0 && nc
 
 hipError_t ce_tail(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
                    float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                   int defer_stats, float* dbias, float label_smoothing) {
+                   int defer_stats, float* dbias, float label_smoothing, const int32_t* labels2, const float* lam) {
+  if ((labels2 != nullptr) != (lam != nullptr)) return hipErrorInvalidValue;
+  if (labels2)
+    return ce_tail_mix(x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats, work, st, defer_stats, dbias,
+                       label_smoothing, labels2, lam);
   if (label_smoothing != 0.f)
     return ce_tail_smooth(x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats, work, st, defer_stats, dbias,
                           label_smoothing);
@@ -821,7 +922,11 @@ hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1,
                     int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
                     bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
                     float* stats, float* work, hipStream_t st, int defer_stats, float* dbias, float label_smoothing,
-                    const HeadDrop* drop) {
+                    const HeadDrop* drop, const int32_t* labels2, const float* lam) {
+  if ((labels2 != nullptr) != (lam != nullptr)) return hipErrorInvalidValue;
+  if (labels2)
+    return mlp_head_mix(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx,
+                        stats, work, st, defer_stats, dbias, label_smoothing, labels2, lam, drop);
   if (drop)
     return mlp_head_drop(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx,
                          stats, work, st, defer_stats, dbias, label_smoothing, *drop);

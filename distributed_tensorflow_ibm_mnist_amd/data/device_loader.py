@@ -25,7 +25,9 @@ import torch
 
 from ..ops._ext import kernels
 from . import augment as aug
+from . import mix as mixref
 from .augment import AugmentConfig
+from .mix import MixConfig
 
 
 def gather_into(ds: "DeviceDataset", idx: torch.Tensor, out_images: torch.Tensor, out_labels: torch.Tensor) -> None:
@@ -73,6 +75,39 @@ def augment_into(ds: "DeviceDataset", idx: torch.Tensor, out_images: torch.Tenso
     x = x.astype("float32") if out_images.dtype == torch.float32 else aug.f32_round_to_odd(x)
     out_images.view(-1)[: nb * ds.hw * cdst].copy_(torch.from_numpy(x).reshape(-1))
     out_labels[:nb].copy_(ds.labels[idx])
+
+
+@functools.lru_cache(maxsize=8)
+def _mix_tables(mixup_alpha: float, cutmix_alpha: float, device: str):
+    """(lam_table, side_table) of the two alphas as the device tensors the binding takes (None for an
+    alpha of 0), computed and uploaded once."""
+    dev = torch.device(device)
+    T = torch.from_numpy(mixref.lam_table(mixup_alpha)).to(dev) if mixup_alpha != 0.0 else None
+    S = torch.from_numpy(mixref.side_table(cutmix_alpha)).to(dev) if cutmix_alpha != 0.0 else None
+    return T, S
+
+
+def mix_into(out_images: torch.Tensor, out_labels: torch.Tensor, out_labels2: torch.Tensor, out_lam: torch.Tensor,
+             nb: int, cfg: MixConfig, pos0: int) -> None:
+    """Mixup / CutMix of ``data/mix.py`` in place on the first ``nb`` entries of the gathered (or augmented)
+    batch: entry b is mixed with entry nb - 1 - b as ``(cfg.seed, pos0 + b)`` draws it, and rows < nb of
+    ``out_labels2`` / ``out_lam`` receive the second label and the weight.  The ``mix_images`` HIP kernel
+    on the GPU (one launch, bf16 buffers); on CPU the host reference ``mixed`` rounded once to the
+    buffer's dtype."""
+    cdst = int(out_images.shape[-1])
+    if out_images.device.type == "cuda":
+        if out_images.dtype != torch.bfloat16:
+            raise ValueError(f"mixing on the device needs a bf16 input buffer, got {out_images.dtype}")
+        T, S = _mix_tables(cfg.mixup_alpha, cfg.cutmix_alpha, str(out_images.device))
+        kernels().mix_images(out_images, out_labels, out_labels2, out_lam, nb, cdst, int(pos0), cfg.seed, cfg.thr_p,
+                             lam_table=T, side_table=S)
+        return
+    flat = out_images.view(-1)[: nb * 784 * cdst]
+    x, l2, lam = mixref.mixed(flat.view(nb, 784, cdst).float().numpy(), out_labels[:nb].numpy(), cfg, pos0)
+    x = x.astype("float32") if out_images.dtype == torch.float32 else aug.f32_round_to_odd(x)
+    flat.copy_(torch.from_numpy(x).reshape(-1))
+    out_labels2[:nb].copy_(torch.from_numpy(l2))
+    out_lam[:nb].copy_(torch.from_numpy(lam))
 
 
 class DeviceDataset:
@@ -168,14 +203,37 @@ def perm_positions(start: int, n: int, N: int, seed: int, device=None, out: Opti
 class DeviceLoader:
     def __init__(self, ds: DeviceDataset, out_images: torch.Tensor, out_labels: torch.Tensor, rank: int = 0,
                  world: int = 1, seed: int = 0, shard: bool = True, shuffle: bool = True,
-                 idx_out: Optional[torch.Tensor] = None, augment: Optional[AugmentConfig] = None):
+                 idx_out: Optional[torch.Tensor] = None, augment: Optional[AugmentConfig] = None,
+                 mix: Optional[MixConfig] = None, out_labels2: Optional[torch.Tensor] = None,
+                 out_lam: Optional[torch.Tensor] = None):
         """``idx_out``: instead of gathering + normalising images into ``out_images``,
         write the batch's dataset indices there (the first fused conv reads the
         uint8 dataset itself: HipNet.bind_u8_input); labels are still gathered.
         ``augment``: every batch entry is shifted / rotated / zoomed as ``data/augment.py``
         draws it from (seed, global stream position); the rows are the ones an un-augmented
         loader gathers.  Needs the gathered-image path (``idx_out`` None); a config with all
-        three amounts 0 is no augmentation."""
+        three amounts 0 is no augmentation.
+        ``mix``: mixup / CutMix (``data/mix.py``) of every local batch with its own flip, in place after
+        the batch is gathered (or augmented), drawn from (seed, global stream position) -- sharded ranks
+        need no seed of their own; ``out_labels2`` (int32 [B]) and ``out_lam`` (fp32 [B]) receive the
+        second label and the weight of every row.  Needs the gathered-image path too; a config that
+        mixes nothing (both alphas 0, or ``mix_prob`` 0) is no mixing."""
+        if mix is not None and not mix.enabled:
+            mix = None
+        if mix is not None and idx_out is not None:
+            raise ValueError("mix needs the gathered-image input path: idx_out must be None (a fused first "
+                             "conv gathers unmixed dataset rows)")
+        if mix is not None and (out_labels2 is None or out_lam is None):
+            raise ValueError("mix needs out_labels2 and out_lam (the net's labels2 / mix_lam buffers)")
+        if mix is not None and (ds.hw != 784 or int(out_images.shape[-1]) not in (1, 3)):
+            raise ValueError(f"mix needs 28x28 images with 1 or 3 channels, got hw={ds.hw}, "
+                             f"Cdst={int(out_images.shape[-1])}")
+        if mix is not None and (out_labels2.dtype != torch.int32 or out_lam.dtype != torch.float32
+                                or out_labels2.shape != out_labels.shape or out_lam.shape != out_labels.shape):
+            raise ValueError("mix: out_labels2 must be int32 and out_lam float32, both of out_labels' shape")
+        if mix is not None and not shard:   # unsharded ranks: own draws, as own orders
+            mix = mix.with_seed((mix.seed + 7919 * rank) % (1 << 63))
+        self.mix, self.out_labels2, self.out_lam = mix, out_labels2, out_lam
         if augment is not None and not augment.enabled:
             augment = None
         if augment is not None and idx_out is not None:
@@ -214,7 +272,7 @@ class DeviceLoader:
         nothing.  Only for the resident-dataset shuffle (``idx_out``) with full batches, and
         only where nothing else writes the index / label buffers between the optimizer and
         the next ``next()`` (bench.py; not the CLI loop, which evaluates into them)."""
-        if self.augment is not None:
+        if self.augment is not None or self.mix is not None:
             return None
         if not (self.shuffle and self.idx_out is not None and self.idx_out.is_cuda and self.ds.device.type == "cuda"):
             return None
@@ -241,6 +299,7 @@ class DeviceLoader:
             else:
                 idx = torch.remainder(torch.arange(start, start + nb, device=self.ds.device), N)
             augment_into(self.ds, idx, self.out_images, self.out_labels, self.augment, start)
+            self._mix(nb, start)
             self.pos += self.global_batch
             return nb
         if (self.shuffle and self.idx_out is None and self.ds.device.type == "cuda" and self.ds.hw == 784
@@ -248,6 +307,7 @@ class DeviceLoader:
             # one kernel: Feistel row + gather + normalise (+ labels)
             kernels().prep_images_perm(self.ds.images, self.ds.labels, self.out_images, self.out_labels, nb,
                                        int(start), int(self.seed), _half_bits(N))
+            self._mix(nb, start)
             self.pos += self.global_batch
             return nb
         if self.shuffle and self.idx_out is not None and self.idx_out.is_cuda:
@@ -265,8 +325,14 @@ class DeviceLoader:
             torch.index_select(self.ds.labels, 0, idx, out=self.out_labels[:nb])
         else:
             gather_into(self.ds, idx, self.out_images, self.out_labels)
+            self._mix(nb, start)
         self.pos += self.global_batch
         return nb
+
+    def _mix(self, nb: int, start: int) -> None:
+        """The one mix launch of a batch, after whatever wrote the buffer; outside any captured step."""
+        if self.mix is not None:
+            mix_into(self.out_images, self.out_labels, self.out_labels2, self.out_lam, nb, self.mix, start)
 
 
 def eval_batches(ds: DeviceDataset, out_images: torch.Tensor, out_labels: torch.Tensor) -> Iterator[int]:

@@ -109,16 +109,34 @@ def forward(spec: ModelSpec, params: Dict[str, torch.Tensor], x: torch.Tensor,
     return x, acts
 
 
+def two_label_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, labels2: torch.Tensor, lam: torch.Tensor,
+                            label_smoothing: float = 0.0) -> torch.Tensor:
+    """The mixup / CutMix loss per row: lam CE(labels) + (1 - lam) CE(labels2), the smoothing applied to
+    both; a row with lam == 1 takes CE(labels) alone (an infinite logit at labels2 leaves it finite)."""
+    lam = lam.to(logits.dtype)
+    ca = F.cross_entropy(logits, labels.long(), label_smoothing=label_smoothing, reduction="none")
+    cb = F.cross_entropy(logits, labels2.long(), label_smoothing=label_smoothing, reduction="none")
+    return torch.where(lam < 1, lam * ca + (1 - lam) * cb, ca)
+
+
 def losses(spec: ModelSpec, params: Dict[str, torch.Tensor], logits: torch.Tensor,
-           labels: torch.Tensor, label_smoothing: float = 0.0) -> Dict[str, torch.Tensor]:
+           labels: torch.Tensor, label_smoothing: float = 0.0, labels2: Optional[torch.Tensor] = None,
+           lam: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """All entries of the reference 'losses' collection plus total_loss (``label_smoothing``:
-    the training form of ``cross_entropy``, against (1 - eps) * onehot + eps / classes)."""
+    the training form of ``cross_entropy``, against (1 - eps) * onehot + eps / classes).
+    ``labels2`` and ``lam`` (together): the mixup / CutMix loss mean(lam CE(labels) + (1 - lam) CE(labels2)),
+    the smoothing applied to both; a row with lam == 1 takes CE(labels) alone."""
+    if (labels2 is None) != (lam is None):
+        raise ValueError(f"labels2 and lam come together, got {'labels2' if lam is None else 'lam'} alone")
     out: Dict[str, torch.Tensor] = {}
     for L in spec.weights():
         if L.wd is not None:
             wgt = params[f"{L.name}/weights"]
             out[f"{L.name}/weight_loss"] = float(L.wd) * 0.5 * (wgt * wgt).sum()
-    out["cross_entropy"] = F.cross_entropy(logits, labels.long(), label_smoothing=label_smoothing)
+    if labels2 is not None:
+        out["cross_entropy"] = two_label_cross_entropy(logits, labels, labels2, lam, label_smoothing).mean()
+    else:
+        out["cross_entropy"] = F.cross_entropy(logits, labels.long(), label_smoothing=label_smoothing)
     out["total_loss"] = sum(out.values())
     return out
 

@@ -167,14 +167,19 @@ class LRNFn(torch.autograd.Function):
 class SoftmaxCrossEntropyFn(torch.autograd.Function):
     """Mean sparse softmax cross-entropy; the same kernel pass produces dlogits,
     the top-1 correct count and a non-finite flag (returned as ``stats``).  With
-    ``label_smoothing`` the loss (and stats[0]) is the smoothed one."""
+    ``label_smoothing`` the loss (and stats[0]) is the smoothed one; with ``labels2`` and ``lam`` it is
+    the two-label loss of mixup / CutMix."""
 
     @staticmethod
-    def forward(ctx, logits, labels, n_classes: int, label_smoothing: float = 0.0):
+    def forward(ctx, logits, labels, n_classes: int, label_smoothing: float = 0.0, labels2=None, lam=None):
         logits = logits.float().contiguous()
         B = logits.shape[0]
+        if (labels2 is None) != (lam is None):
+            raise ValueError(f"y2 and lam come together, got {'y2' if lam is None else 'lam'} alone")
+        if labels2 is not None:
+            labels2, lam = labels2.to(torch.int32).contiguous(), lam.to(torch.float32).contiguous()
         dl, stats = Fk.softmax_ce(logits, labels.to(torch.int32).contiguous(), n_classes, scale=1.0 / B,
-                                  label_smoothing=label_smoothing)
+                                  label_smoothing=label_smoothing, labels2=labels2, lam=lam)
         ctx.save_for_backward(dl)
         ctx.mark_non_differentiable(stats)
         return stats[0] / B, stats
@@ -182,7 +187,7 @@ class SoftmaxCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dstats):
         (dl,) = ctx.saved_tensors
-        return dl.float() * dloss, None, None, None
+        return dl.float() * dloss, None, None, None, None, None
 
 
 class DropoutFn(torch.autograd.Function):
@@ -231,9 +236,10 @@ def lrn(x, r: int = 4, bias: float = 1.0, alpha: float = 0.001 / 9.0, beta: floa
     return LRNFn.apply(x, r, bias, alpha, beta)
 
 
-def softmax_cross_entropy(logits, labels, n_classes: int, label_smoothing: float = 0.0):
-    """Returns (mean loss, stats f32[8]: [sum CE, #correct, nonfinite flag, ...])."""
-    return SoftmaxCrossEntropyFn.apply(logits, labels, n_classes, label_smoothing)
+def softmax_cross_entropy(logits, labels, n_classes: int, label_smoothing: float = 0.0, labels2=None, lam=None):
+    """Returns (mean loss, stats f32[8]: [sum CE, #correct, nonfinite flag, ...]).  ``labels2`` / ``lam``
+    (together): the two-label loss mean(lam CE(labels) + (1 - lam) CE(labels2)) of mixup / CutMix."""
+    return SoftmaxCrossEntropyFn.apply(logits, labels, n_classes, label_smoothing, labels2, lam)
 
 
 def dropout(x, step, seed: int, layer: int, p: float):

@@ -78,8 +78,10 @@ class SoftmaxCrossEntropy(nn.Module):
         self.n_classes, self.label_smoothing = n_classes, float(label_smoothing)
         self.last_stats: Optional[torch.Tensor] = None
 
-    def forward(self, logits, labels):
-        loss, stats = A.softmax_cross_entropy(logits, labels, self.n_classes, self.label_smoothing)
+    def forward(self, logits, y, y2=None, lam=None):
+        """``y2`` (a second label per row) and ``lam`` (the weight of ``y``), together or not at all:
+        the loss of mixup / CutMix, mean(lam CE(y) + (1 - lam) CE(y2))."""
+        loss, stats = A.softmax_cross_entropy(logits, y, self.n_classes, self.label_smoothing, y2, lam)
         self.last_stats = stats
         return loss
 

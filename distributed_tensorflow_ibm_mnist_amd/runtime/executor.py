@@ -418,6 +418,13 @@ class HipNet:
         H, W = spec.input_hw
         self.x0 = _bf16(batch, H, W, spec.in_channels, device=dev)
         self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+        # mixup / CutMix: the second label and the weight of the first per row, written by the loader's
+        # mix launch (DeviceLoader(out_labels2=, out_lam=)) and read by the training loss alone
+        self.labels2: Optional[torch.Tensor] = None
+        self.mix_lam: Optional[torch.Tensor] = None
+        if self.opt.mix:
+            self.labels2 = torch.zeros(batch, dtype=torch.int32, device=dev)
+            self.mix_lam = torch.ones(batch, dtype=torch.float32, device=dev)
         self.layers: List[_Layer] = []
         x, in_relu = self.x0, False
         n = len(spec.layers)
@@ -659,13 +666,15 @@ class HipNet:
         if grads and self._drop_pass and self.head_kind == "mlp":
             drop = dict(dropout=self.opt.dropout, drop_step=self.fp.step, drop_seed=self.opt.dropout_seed,
                         drop_layer3=self.layers[i].idx, drop_layer4=self.layers[i + 1].idx)
+        # and so do the two labels of mixup / CutMix: fixed buffers, so a captured step replays them
+        mix = dict(labels2=self.labels2, lam=self.mix_lam) if (grads and self.opt.mix) else {}
         if self.head_kind == "tail":
             l5 = self.layers[i]
             K = kernels()
             K.ce_tail(l5.x, self.fp.bf16t_view(l5.wname), self.fp.param_view(l5.bname), l5.spec.dout, self.labels,
                       nb, scale, l5.out, dl=self.dlogits if grads else None, dx=self.dbuf[i] if grads else None,
                       stats=stats, work=self.ce_work, defer_stats=defer, dbias=self.ce_dbias if grads else None,
-                      label_smoothing=eps)
+                      label_smoothing=eps, **mix)
             if grads:
                 l5.ce_bias = (self.ce_dbias, K.ce_tail_blocks(nb))
             if defer:
@@ -680,7 +689,7 @@ class HipNet:
                            dl=self.dlogits if grads else None, dh4=self.dbuf[i + 2] if grads else None,
                            dh3=self.dbuf[i + 1] if grads else None, dx=self.dbuf[i] if grads else None,
                            stats=stats, work=self.ce_work, defer_stats=defer,
-                           dbias=self.ce_dbias if grads else None, label_smoothing=eps, **drop)
+                           dbias=self.ce_dbias if grads else None, label_smoothing=eps, **drop, **mix)
         if grads:
             l5.ce_bias = (self.ce_dbias, kernels().mlp_head_blocks(nb))
         if defer:
@@ -796,11 +805,12 @@ class HipNet:
         # training statistics deferred to this step's finalize_k, as for the fused head
         ld = self.logits.shape[1]
         nblk = kernels().softmax_ce_dbias_blocks(nb, ld)
+        mix = dict(labels2=self.labels2, lam=self.mix_lam) if self.opt.mix else {}
         self._ce_defer_blocks = kernels().softmax_ce(
             self.logits, ld, self.labels, nb, self.n_classes,
             (1.0 / nb) if scale is None else scale, self.dlogits, ld, self.stats,
             None, self.ce_work, defer_stats=self.ce_work is not None,
-            dbias=self.ce_dbias if nblk > 0 else None, label_smoothing=self.opt.label_smoothing)
+            dbias=self.ce_dbias if nblk > 0 else None, label_smoothing=self.opt.label_smoothing, **mix)
         self.layers[-1].ce_bias = (self.ce_dbias, nblk) if nblk > 0 else None
 
     def backward(self, nb: Optional[int] = None) -> None:

@@ -282,6 +282,9 @@ class HipNetF32:
         cover the geometry (ConvPoolF, LRNPoolF); False keeps the reference's layer-by-layer
         graph (tests compare the two)."""
         dev = torch.device(device)
+        if opt is not None and opt.mix:     # the two-label loss is in the bf16 softmax-CE kernels alone
+            raise ValueError("mixup_alpha / cutmix_alpha are not supported by the fp32 executor (--precision=fp32): "
+                             "use the bf16 executor, or leave both at 0")
         assert dev.type == "cuda", "HipNetF32 runs the HIP kernels (use --impl=torch on CPU)"
         self.spec, self.B, self.device = spec, batch, dev
         self.opt = opt or OptConfig()

@@ -77,8 +77,15 @@ class OptConfig:
     # layer, row, feature) (ops/dropout.py), so there is no state.  0: nothing extra is launched.
     dropout: float = 0.0
     dropout_seed: int = 0
+    # mixup / CutMix (data/mix.py): the training loss takes a second label and a weight per row, which
+    # the loader's mix launch writes into the net's ``labels2`` and ``mix_lam`` buffers; eval paths keep
+    # the hard labels.  The draw itself is the loader's (MixConfig); this flag only says that the
+    # training loss reads the two buffers.  False: nothing is allocated, the launches are today's.
+    mix: bool = False
 
     def __post_init__(self):
+        if not isinstance(self.mix, (bool,)):
+            raise ValueError(f"mix must be a bool, got {self.mix!r}")
         from ..ops.dropout import check_rate, check_seed
         self.dropout = check_rate(self.dropout, "dropout")
         self.dropout_seed = check_seed(self.dropout_seed, "dropout_seed")
@@ -131,7 +138,8 @@ class OptConfig:
 
     @staticmethod
     def from_spec(spec, decay_steps: int, decay_rate: float, ema: float = 0.9999,
-                  label_smoothing: float = 0.0, dropout: float = 0.0, dropout_seed: int = 0) -> "OptConfig":
+                  label_smoothing: float = 0.0, dropout: float = 0.0, dropout_seed: int = 0,
+                  mix: bool = False) -> "OptConfig":
         """From a parameter-manager ``OptimizerSpec`` (which does not carry ``label_smoothing`` or
         the dropout keys: the caller passes ``getLabelSmoothing()``, ``getDropout()`` and the seed)."""
         lr = spec.learning_rate
@@ -149,7 +157,7 @@ class OptConfig:
                          warmup_steps=getattr(spec, "warmup_steps", 0),
                          total_steps=getattr(spec, "lr_total_steps", 0),
                          lr_end=getattr(spec, "lr_end", 0.0), lr_power=getattr(spec, "lr_power", 1.0),
-                         label_smoothing=label_smoothing, dropout=dropout, dropout_seed=dropout_seed)
+                         label_smoothing=label_smoothing, dropout=dropout, dropout_seed=dropout_seed, mix=mix)
 
     @property
     def scheduled(self) -> bool:

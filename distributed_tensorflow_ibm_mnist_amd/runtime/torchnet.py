@@ -147,6 +147,12 @@ class TorchNet:
         xdt = torch.bfloat16 if dev.type == "cuda" else torch.float32
         self.x0 = torch.zeros(batch, H, W, spec.in_channels, dtype=xdt, device=dev)
         self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+        # mixup / CutMix: the loader's second labels and weights, read by the training loss alone
+        self.labels2: Optional[torch.Tensor] = None
+        self.mix_lam: Optional[torch.Tensor] = None
+        if self.opt.mix:
+            self.labels2 = torch.zeros(batch, dtype=torch.int32, device=dev)
+            self.mix_lam = torch.ones(batch, dtype=torch.float32, device=dev)
         self.stats = torch.zeros(8, dtype=torch.float32, device=dev)
         self.eval_stats = torch.zeros(8, dtype=torch.float32, device=dev)
         names = [e.name for e in self.fp.wd_entries]
@@ -192,7 +198,11 @@ class TorchNet:
             self.forward(nb, grad=True)
         lab = self.labels[:nb].long()
         # the training loss (and its cross_entropy scalar) is the smoothed one; eval_batch is not
-        loss = F.cross_entropy(self._logits, lab, reduction="sum", label_smoothing=self.opt.label_smoothing)
+        if self.opt.mix:    # torch_ref.losses' two-label form, as a sum over the rows
+            loss = torch_ref.two_label_cross_entropy(self._logits, lab, self.labels2[:nb], self.mix_lam[:nb],
+                                                     self.opt.label_smoothing).sum()
+        else:
+            loss = F.cross_entropy(self._logits, lab, reduction="sum", label_smoothing=self.opt.label_smoothing)
         with torch.no_grad():
             self.stats[0] += loss.detach()
             self.stats[1] += _in_top1(self._logits, lab)

@@ -101,9 +101,11 @@ class Replica:
                  eval_images: Optional[torch.Tensor] = None, eval_labels: Optional[torch.Tensor] = None,
                  seed: int = 0, shard: bool = True, use_graph: bool = True, bucket_mb: float = 4.0,
                  group=None, standalone: bool = False, fused_input=False, precision: str = "bf16",
-                 dp_graph: bool = False, augment=None, log=print):
+                 dp_graph: bool = False, augment=None, mix=None, log=print):
         """``augment``: a ``data.augment.AugmentConfig``; when any of its amounts is non-zero the
-        training batches (and only those) are shifted / rotated / zoomed on the device."""
+        training batches (and only those) are shifted / rotated / zoomed on the device.
+        ``mix``: a ``data.mix.MixConfig``; when it mixes anything, ``opt.mix`` must be set (the net then
+        holds ``labels2`` / ``mix_lam``) and the training batches are mixed by the loader."""
         self.spec, self.impl, self.B, self.device = spec, impl, batch, torch.device(device)
         self.net = build_net(impl, spec, batch, self.device, init, opt, precision)
         # standalone: a parameter-server worker (no data-parallel group of its own)
@@ -122,6 +124,13 @@ class Replica:
             # the first fused conv can only gather un-augmented dataset rows
             log(f"augmentation is on: input mode {mode!r} -> 'prep' (the augmentation kernel writes the input buffer)")
             mode = "prep"
+        self.mix = mix if mix is not None and mix.enabled else None
+        if self.mix is not None and not opt.mix:
+            raise ValueError("a MixConfig that mixes needs OptConfig(mix=True): the training loss reads two labels")
+        if self.mix is not None and mode != "prep":
+            # the first fused conv can only gather unmixed dataset rows
+            log(f"mixup / CutMix is on: input mode {mode!r} -> 'prep' (the mix kernel works on the input buffer)")
+            mode = "prep"
         # eligibility first: a model that cannot gather (3-channel input, fp32 executor) never
         # gets a normalised bf16 copy of the whole split built for nothing
         fused_in = (impl == "hip" and mode != "prep" and getattr(self.net, "can_gather_input", lambda: True)()
@@ -129,7 +138,9 @@ class Replica:
                                                 bwd_images=None if mode == "u8" else self.train_ds.images))
         self.loader = DeviceLoader(self.train_ds, self.net.x0, self.net.labels, rank=self.rank, world=self.world,
                                    seed=seed, shard=shard, idx_out=self.net.idx_buf if fused_in else None,
-                                   augment=self.augment)
+                                   augment=self.augment, mix=self.mix,
+                                   out_labels2=getattr(self.net, "labels2", None),
+                                   out_lam=getattr(self.net, "mix_lam", None))
         # hipGraph: single replica, or (dp_graph) the DP step with its RCCL all-reduces captured
         self.use_graph = (use_graph and impl == "hip" and self.device.type == "cuda"
                           and (self.world == 1 or (dp_graph and dist.get_backend(group) == "nccl")))

@@ -108,10 +108,14 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
                               MOVING_AVERAGE_DECAY, label_smoothing=pm.getLabelSmoothing(),
                               # data parallel: rank r draws its own masks from dropout_seed + r (no state to broadcast)
                               dropout=pm.getDropout(),
-                              dropout_seed=pm.getDropoutSeed(FLAGS.seed) + (cl.rank if cl.mode == "dp" else 0))
+                              dropout_seed=pm.getDropoutSeed(FLAGS.seed) + (cl.rank if cl.mode == "dp" else 0),
+                              # mixup / CutMix: the training loss takes two labels (the draw is the loader's)
+                              mix=pm.getMix(FLAGS.seed).enabled)
     # training-input augmentation: drawn per (augment_seed, stream position), so sharded ranks differ
     # without a per-rank seed (an unsharded loader offsets the seed itself, as it does for the shuffle)
     augment = pm.getAugment(FLAGS.seed)
+    # mixup / CutMix: drawn per (mix_seed, stream position) too
+    mix = pm.getMix(FLAGS.seed)
     init = torch_ref.init_params(spec, seed=FLAGS.seed)
     if cl.mode == "ps" and cl.job_name == "ps":
         from ..ckpt.saver import Saver, latest_checkpoint
@@ -143,9 +147,9 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
                    seed=FLAGS.seed, shard=not FLAGS.no_shard, use_graph=FLAGS.hip_graph,
                    bucket_mb=FLAGS.bucket_mb, group=dp_group if cl.mode == "dp" else None,
                    fused_input=True if FLAGS.fused_input else getattr(FLAGS, "input_mode", "prep"), precision=getattr(FLAGS, "precision", "bf16"),
-                   dp_graph=getattr(FLAGS, "hip_graph_dp", False), augment=augment, log=log) \
+                   dp_graph=getattr(FLAGS, "hip_graph_dp", False), augment=augment, mix=mix, log=log) \
         if cl.mode != "ps" else _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS,
-                                         augment, log)
+                                         augment, log, mix)
     replica = base
     if cl.mode == "ps":
         from ..parallel.ps import PSWorkerReplica
@@ -210,13 +214,16 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
     return res
 
 
-def _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS, augment=None, log=print):
+def _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS, augment=None, log=print,
+             mix=None):
     """A PS-mode worker: own input stream (reference P3: no sharding), no DP group.  It owns its
-    loader, so it augments its own inputs; the servers never see them."""
+    loader and its loss, so it augments and mixes its own inputs; the servers never see them."""
+    if mix is not None and mix.enabled:
+        mix = mix.with_seed((mix.seed + 7919 * cl.task_id) % (1 << 63))
     if augment is not None and augment.enabled:
         # a standalone replica is rank 0 of its own world: the task id separates the workers' draws,
         # as it separates their data orders
         augment = augment.with_seed((augment.seed + 7919 * cl.task_id) % (1 << 63))
     return Replica(spec, impl, batch_size, cl.device, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev,
                    seed=FLAGS.seed + 7919 * cl.task_id, shard=False, use_graph=False, bucket_mb=FLAGS.bucket_mb,
-                   standalone=True, precision=getattr(FLAGS, "precision", "bf16"), augment=augment, log=log)
+                   standalone=True, precision=getattr(FLAGS, "precision", "bf16"), augment=augment, mix=mix, log=log)

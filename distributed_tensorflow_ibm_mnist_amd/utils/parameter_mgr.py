@@ -24,6 +24,9 @@ overrides:
     getAugmentElasticAlpha() / getAugmentElasticSigma()
                              -> float / float   (elastic distortion: displacement scale, 0: off; smoothing sigma)
     getAugment(default_seed) -> AugmentConfig   (the six keys, checked)
+    getMixupAlpha() / getCutmixAlpha() / getMixProb() / getMixSeed(default)
+                             -> float / float / float / int   (mixup and CutMix of training batches; alpha 0: off)
+    getMix(default_seed)     -> MixConfig   (the four keys, checked)
 
 Defaults are the TF CIFAR-10 tutorial values that ``mnist_input.py`` mirrors
  — they are *chosen* defaults, not numbers the reference
@@ -70,6 +73,10 @@ DEFAULTS: Dict[str, Any] = {
     "augment_seed": None,        # seed of the counter-based augmentation draws; None: the run's seed
     "augment_elastic_alpha": 0.0,   # ... elastic distortion: displacement scale in pixels of the smoothed field (0..64); 0: off
     "augment_elastic_sigma": 4.0,   # ... standard deviation in pixels of the Gaussian that smooths the field (0.5..8)
+    "mixup_alpha": 0.0,          # training batches: mixup with its weight from Beta(a, a) (0.1..8); 0: off
+    "cutmix_alpha": 0.0,         # ... CutMix with the box area from Beta(a, a) (0.1..8); 0: off; both set: one of the two per entry
+    "mix_prob": 1.0,             # ... probability that an entry is mixed at all (0..1)
+    "mix_seed": None,            # seed of the counter-based mixing draws; None: the run's seed
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -156,7 +163,7 @@ FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", 
              "adagrad_initial_accumulator", "clip_norm", "lars_eta", "lr_schedule", "warmup_steps",
              "lr_total_steps", "lr_end", "lr_power", "label_smoothing", "dropout", "dropout_seed",
              "augment_shift", "augment_rotate", "augment_scale", "augment_seed", "augment_elastic_alpha",
-             "augment_elastic_sigma")
+             "augment_elastic_sigma", "mixup_alpha", "cutmix_alpha", "mix_prob", "mix_seed")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
@@ -329,6 +336,38 @@ def getAugment(default_seed: int = 0):
     from ..data.augment import AugmentConfig
     return AugmentConfig(getAugmentShift(), getAugmentRotate(), getAugmentScale(), getAugmentSeed(default_seed),
                          getAugmentElasticAlpha(), getAugmentElasticSigma())
+
+
+def getMixupAlpha() -> float:
+    """The ``mixup_alpha`` key: 0 (off), or finite with 0.1 <= alpha <= 8, Beta(alpha, alpha) of the weight."""
+    from ..data.mix import check_alpha
+    return check_alpha(get("mixup_alpha"), "mixup_alpha")
+
+
+def getCutmixAlpha() -> float:
+    """The ``cutmix_alpha`` key: 0 (off), or finite with 0.1 <= alpha <= 8, Beta(alpha, alpha) behind the box."""
+    from ..data.mix import check_alpha
+    return check_alpha(get("cutmix_alpha"), "cutmix_alpha")
+
+
+def getMixProb() -> float:
+    """The ``mix_prob`` key: finite with 0 <= p <= 1, the probability that an entry is mixed at all."""
+    from ..data.mix import check_prob
+    return check_prob(get("mix_prob"), "mix_prob")
+
+
+def getMixSeed(default: int = 0) -> int:
+    """The ``mix_seed`` key: an integer with 0 <= seed < 2^63; unset: ``default`` (the run's seed)."""
+    from ..ops.dropout import check_seed
+    v = get("mix_seed")
+    return check_seed(default if v is None else v, "mix_seed")
+
+
+def getMix(default_seed: int = 0):
+    """The four mixing keys as a ``data.mix.MixConfig`` (its ``enabled`` says whether anything is mixed).
+    The workers own their loader and their loss, so parameter-server mode takes the keys as they are."""
+    from ..data.mix import MixConfig
+    return MixConfig(getMixupAlpha(), getCutmixAlpha(), getMixProb(), getMixSeed(default_seed))
 
 
 def check_ps_dropout(job_name: str, log=print) -> None:

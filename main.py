@@ -74,6 +74,13 @@ flags.DEFINE_float("augment_elastic_alpha", -1, "training images only: elastic d
                    "of the smoothed random field, 0..64 (0.0: off; -1: unset); on trains in --input_mode prep")
 flags.DEFINE_float("augment_elastic_sigma", -1, "standard deviation in pixels of the Gaussian that smooths the elastic "
                    "field, 0.5..8 (-1: unset, 4.0); read only when augment_elastic_alpha > 0")
+flags.DEFINE_float("mixup_alpha", -1, "training batches only: mixup of every entry with the entry at the flipped batch "
+                   "position, the weight from Beta(a, a), 0.1..8 (0.0: off; -1: unset, the config's value or 0.0)")
+flags.DEFINE_float("cutmix_alpha", -1, "training batches only: CutMix, a box of the partner pasted in, its area from "
+                   "Beta(a, a), 0.1..8 (0.0: off; -1: unset); with mixup_alpha also set each entry takes one of the two")
+flags.DEFINE_float("mix_prob", -1, "probability that a batch entry is mixed at all, 0..1 (-1: unset, 1.0)")
+flags.DEFINE_integer("mix_seed", -1, "seed of the mixing draws (-1: unset, the run's --seed); a draw is a pure function "
+                     "of (seed, stream position), so a resumed run repeats it")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
 flags.DEFINE_string("test_data", "", "override getTestData()")
 flags.DEFINE_string("val_data", "", "override getValData()")
