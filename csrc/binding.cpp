@@ -1222,6 +1222,91 @@ void summary_stats(Tensor src, Tensor segs, Tensor limits, Tensor counts, Tensor
          "summary_stats");
 }
 
+// Confusion matrix, rank histogram and calibration sums of logits[:nb] added to acc_i / acc_f
+// (eval_metrics.hip; the layout is eval_metrics_layout's).  Every refusal is a ValueError raised
+// before anything is launched.
+void eval_metrics(Tensor logits, optional<Tensor> labels, int64_t nb, int64_t n_classes, Tensor acc_i, Tensor acc_f,
+                  Tensor scratch, optional<Tensor> rows, double temperature, int64_t n_bins) {
+  TORCH_CHECK_VALUE(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2,
+                    "logits: a contiguous 2-D GPU tensor [B, ld], got ", logits.dim(), " dimension(s)");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK_VALUE(bf || logits.scalar_type() == at::kFloat, "logits: expected float32 or bfloat16, got ",
+                    logits.scalar_type());
+  const int64_t B = logits.size(0), ld = logits.size(1);
+  TORCH_CHECK_VALUE(n_classes >= 2 && n_classes <= mnistx::EVAL_MAX_CLASSES, "n_classes: needs 2 <= NC <= ",
+                    mnistx::EVAL_MAX_CLASSES, ", got ", n_classes);
+  TORCH_CHECK_VALUE(n_classes <= ld, "n_classes: ", n_classes, " > the logits' row length ", ld);
+  TORCH_CHECK_VALUE(nb >= 0 && nb <= B, "nb: needs 0 <= nb <= B = ", B, ", got ", nb);
+  TORCH_CHECK_VALUE(B < ((int64_t)1 << 31) - 256, "logits: 2^31 rows or more");
+  TORCH_CHECK_VALUE(std::isfinite(temperature) && temperature > 0.0 && (float)temperature > 0.f &&
+                        std::isfinite((float)temperature) && std::isfinite(1.0f / (float)temperature),
+                    "temperature: must be finite and > 0 (and so must 1 / T in fp32), got ", temperature);
+  TORCH_CHECK_VALUE(n_bins >= 1 && n_bins <= mnistx::EVAL_MAX_BINS, "n_bins: needs 1 <= NB <= ",
+                    mnistx::EVAL_MAX_BINS, ", got ", n_bins);
+  const mnistx::EvalLayout lay = mnistx::eval_metrics_layout((int)n_classes, (int)n_bins);
+  const int32_t* lab = nullptr;
+  if (labels.has_value() && labels->defined()) {
+    TORCH_CHECK_VALUE(labels->is_cuda() && labels->scalar_type() == at::kInt && labels->is_contiguous() &&
+                          labels->numel() >= nb && labels->device() == logits.device(),
+                      "labels: a contiguous int32 tensor of at least nb = ", nb, " elements on the logits' device, has ",
+                      labels->numel(), " of ", labels->scalar_type());
+    lab = P<const int32_t>(*labels);
+  }
+  TORCH_CHECK_VALUE(acc_i.is_cuda() && acc_i.scalar_type() == at::kLong && acc_i.is_contiguous() &&
+                        acc_i.numel() >= lay.size_i,
+                    "acc_i: a contiguous int64 GPU tensor of ", lay.size_i, " elements, has ", acc_i.numel(), " of ",
+                    acc_i.scalar_type());
+  TORCH_CHECK_VALUE(acc_f.is_cuda() && acc_f.scalar_type() == at::kDouble && acc_f.is_contiguous() &&
+                        acc_f.numel() >= lay.size_f,
+                    "acc_f: a contiguous float64 GPU tensor of ", lay.size_f, " elements, has ", acc_f.numel(), " of ",
+                    acc_f.scalar_type());
+  const int64_t ns = mnistx::eval_metrics_scratch_size((int)n_bins);
+  TORCH_CHECK_VALUE(scratch.is_cuda() && scratch.scalar_type() == at::kDouble && scratch.is_contiguous() &&
+                        scratch.numel() >= ns,
+                    "scratch: a contiguous float64 GPU tensor of eval_metrics_scratch_size(n_bins) = ", ns, ", has ",
+                    scratch.numel(), " of ", scratch.scalar_type());
+  int32_t* rw = nullptr;
+  if (rows.has_value() && rows->defined()) {
+    TORCH_CHECK_VALUE(rows->is_cuda() && rows->scalar_type() == at::kInt && rows->is_contiguous() &&
+                          rows->numel() >= nb * 4 && rows->device() == logits.device() &&
+                          reinterpret_cast<uintptr_t>(rows->data_ptr()) % 16 == 0,
+                      "rows: a contiguous 16-byte aligned int32 tensor of at least nb * 4 = ", nb * 4,
+                      " elements on the logits' device, has ", rows->numel(), " of ", rows->scalar_type());
+    rw = P<int32_t>(*rows);
+  }
+  TORCH_CHECK_VALUE(acc_i.device() == logits.device() && acc_f.device() == logits.device() &&
+                        scratch.device() == logits.device(), "acc_i / acc_f / scratch: on the logits' device");
+  TORCH_CHECK_VALUE(reinterpret_cast<uintptr_t>(acc_i.data_ptr()) % 8 == 0 &&
+                        reinterpret_cast<uintptr_t>(acc_f.data_ptr()) % 8 == 0 &&
+                        reinterpret_cast<uintptr_t>(scratch.data_ptr()) % 8 == 0 &&
+                        reinterpret_cast<uintptr_t>(logits.data_ptr()) % (bf ? 2 : 4) == 0,
+                    "logits / acc_i / acc_f / scratch: must be aligned to their element size");
+  if (nb == 0) return;
+  hip_ok(mnistx::eval_metrics(logits.data_ptr(), bf, ld, lab, (int)nb, (int)n_classes, (float)temperature, (int)n_bins,
+                              P<int64_t>(acc_i), P<double>(acc_f), P<double>(scratch), rw, cur_stream()),
+         "eval_metrics");
+}
+
+pybind11::dict eval_metrics_layout(int64_t n_classes, int64_t n_bins) {
+  TORCH_CHECK_VALUE(n_classes >= 2 && n_classes <= mnistx::EVAL_MAX_CLASSES, "n_classes: needs 2 <= NC <= ",
+                    mnistx::EVAL_MAX_CLASSES, ", got ", n_classes);
+  TORCH_CHECK_VALUE(n_bins >= 1 && n_bins <= mnistx::EVAL_MAX_BINS, "n_bins: needs 1 <= NB <= ",
+                    mnistx::EVAL_MAX_BINS, ", got ", n_bins);
+  const mnistx::EvalLayout l = mnistx::eval_metrics_layout((int)n_classes, (int)n_bins);
+  pybind11::dict d;
+  d["confusion"] = l.confusion;
+  d["rank_hist"] = l.rank_hist;
+  d["bin_count"] = l.bin_count;
+  d["bin_correct"] = l.bin_correct;
+  d["counts"] = l.counts;
+  d["size_i"] = l.size_i;
+  d["bin_conf_sum"] = l.bin_conf_sum;
+  d["nll_sum"] = l.nll_sum;
+  d["brier_sum"] = l.brier_sum;
+  d["size_f"] = l.size_f;
+  return d;
+}
+
 mnistx::FinArgs prep_fin(Tensor step, Tensor stats, optional<Tensor> l2, optional<Tensor> wds, int64_t nw,
                          optional<Tensor> loss_ema, int64_t n_ema, int64_t batch, bool increment,
                          optional<Tensor> l2_ranges, optional<Tensor> ce_work, int64_t ce_nblk) {
@@ -1987,6 +2072,20 @@ PYBIND11_MODULE(_kernels, m) {
         "(column NB: NaN, +-inf, above the last limit) and stats[s] = min, max, sum, sum of squares");
   m.def("summary_scratch_size", [](int64_t nseg) { return (int64_t)mnistx::summary_scratch_size((int)nseg); });
   m.def("summary_max_blocks", []() { return (int64_t)mnistx::summary_max_blocks(); });
+  m.def("eval_metrics", &eval_metrics, py::arg("logits"), py::arg("labels"), py::arg("nb"), py::arg("n_classes"),
+        py::arg("acc_i"), py::arg("acc_f"), py::arg("scratch"), py::arg("rows") = py::none(),
+        py::arg("temperature") = 1.0, py::arg("n_bins") = 15,
+        "adds the confusion matrix, rank histogram, reliability bins and NLL / Brier sums of logits[:nb] to "
+        "acc_i (int64) / acc_f (float64), laid out as eval_metrics_layout says; rows [B, 4] int32: per-row "
+        "(pred, rank, bin, bits of conf)");
+  m.def("eval_metrics_layout", &eval_metrics_layout, py::arg("n_classes"), py::arg("n_bins") = 15,
+        "offsets of every accumulator in acc_i / acc_f, and their sizes size_i / size_f");
+  m.def("eval_metrics_scratch_size", [](int64_t n_bins) {
+    TORCH_CHECK_VALUE(n_bins >= 1 && n_bins <= mnistx::EVAL_MAX_BINS, "n_bins: needs 1 <= NB <= ",
+                      mnistx::EVAL_MAX_BINS, ", got ", n_bins);
+    return (int64_t)mnistx::eval_metrics_scratch_size((int)n_bins);
+  }, py::arg("n_bins") = 15);
+  m.def("eval_metrics_max_blocks", []() { return (int64_t)mnistx::eval_metrics_max_blocks(); });
   m.def("set_opt_fin_fused", [](int64_t on) { mnistx::set_opt_fin_fused((int)on); },
         "A/B switch of the optimizer launch running the step's finalize (MNISTX_OPT_FIN_FUSED)");
   m.def("opt_fin_fused_enabled", []() { return mnistx::opt_fin_fused_enabled() != 0; });

@@ -604,4 +604,30 @@ hipError_t summary_stats(const void* src, bool src_bf16, const SummarySeg* segs,
                          const uint16_t* start, int NB, float divisor, int* counts, double* stats, double* scratch,
                          hipStream_t st);
 
+// ---- eval_metrics.hip: confusion matrix, top-k ranks and calibration sums of a batch of logits
+// (obs/eval_metrics.py holds the definitions and the float64 host reference).
+// logits [B][ld] fp32 or bf16 with NC real classes (2 <= NC <= EVAL_MAX_CLASSES, NC <= ld; the
+// columns from NC on are never read), labels int32 [B] or null, rows 0 .. nb - 1 are read.
+// Everything is ADDED to accumulators the caller zeroed, laid out as EvalLayout says:
+//   acc_i int64 [size_i]: confusion [(NC + 1)][NC] (row NC: rows without a label in 0 .. NC - 1),
+//                         rank_hist [NC], bin_count [NB], bin_correct [NB],
+//                         counts [3] = rows seen, labelled rows, bad rows (a non-finite logit);
+//   acc_f float64 [size_f]: bin_conf_sum [NB], nll_sum, brier_sum.
+// scratch: eval_metrics_scratch_size(NB) doubles, the per-block partials of the float64 sums,
+// added in block order by a second launch.  rows (or null) int32 [B][4], 16-byte aligned:
+// (pred, rank, bin, fp32 bits of conf) of every row < nb.  Two passes from zeroed accumulators
+// give the same bits.  nb == 0 launches nothing.
+constexpr int EVAL_MAX_CLASSES = 64;
+constexpr int EVAL_MAX_BINS = 64;
+struct EvalLayout {
+  int confusion, rank_hist, bin_count, bin_correct, counts, size_i;
+  int bin_conf_sum, nll_sum, brier_sum, size_f;
+};
+EvalLayout eval_metrics_layout(int NC, int NB);
+int eval_metrics_max_blocks();
+int64_t eval_metrics_scratch_size(int NB);
+hipError_t eval_metrics(const void* logits, bool logits_bf16, int64_t ld, const int32_t* labels, int nb, int NC,
+                        float temperature, int NB, int64_t* acc_i, double* acc_f, double* scratch, int32_t* rows,
+                        hipStream_t st);
+
 }  // namespace mnistx

@@ -20,7 +20,9 @@ live output buffers.  Channel padding is stripped.
 """
 from __future__ import annotations
 
+import json
 import math
+import os
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -34,7 +36,8 @@ DLMAO_TEST_SUMMARIES = "DLMAO_TEST_SUMMARIES"
 
 class Monitor:
     def __init__(self, log_dir: str, test_interval: int, max_steps: int, replica, sample: int = 64,
-                 eval_examples: Optional[int] = 10000, log=print, device_summaries: bool = False):
+                 eval_examples: Optional[int] = 10000, log=print, device_summaries: bool = False,
+                 eval_metrics: bool = False):
         self.log_dir = log_dir
         self.test_interval, self.max_steps = test_interval, max_steps
         self.replica = replica
@@ -51,6 +54,10 @@ class Monitor:
         self.device_summaries = bool(device_summaries)
         self._kinds: Dict[str, Tuple[str, str]] = {}
         self._summarizer = None
+        # eval_metrics: write_test also evaluates obs/eval_metrics.py's metrics (on the device
+        # for a HIP executor), appends their scalars after the registered test tags and one JSON
+        # line per write to <log_dir>/eval_metrics.jsonl
+        self.eval_metrics = bool(eval_metrics)
 
     # ---- registration API (names as in monitor_cb) ------------------------
     def _fp(self):
@@ -239,13 +246,31 @@ class Monitor:
         if vals:
             self.writer.add_summary(summary(vals), step)
 
+    def _metric_values(self, m: Dict[str, object]) -> List[bytes]:
+        vals = [scalar_value(f"test {k} accuracy", float(m[k])) for k in ("top2", "top3") if k in m]
+        vals += [scalar_value(f"test {k}", float(m[k])) for k in ("nll", "brier", "ece", "mce", "macro_f1")]
+        vals += [scalar_value(f"test recall/{c}", float(v)) for c, v in enumerate(m["recall"])]
+        vals += [scalar_value(f"test precision/{c}", float(v)) for c, v in enumerate(m["precision"])]
+        return vals
+
     def write_test(self, step: int) -> None:
-        res = self.replica.evaluate(self.eval_examples)
+        if not self.eval_metrics:
+            res = self.replica.evaluate(self.eval_examples)
+        else:
+            res = self.replica.evaluate(self.eval_examples, metrics=True)
         self._test_cache = res
         vals = [fn() for _, fn in self._test]
+        m = res.get("metrics") if self.eval_metrics else None
+        if m is not None:
+            vals += self._metric_values(m)
         if vals:
             self.writer.add_summary(summary(vals), step)
-        self.log(f"step {step}: test loss {res['loss']:.4f}  test accuracy {res['accuracy']:.4f}")
+        line = f"step {step}: test loss {res['loss']:.4f}  test accuracy {res['accuracy']:.4f}"
+        if m is not None:
+            line += f"  ECE {m['ece']:.4f}  macro-F1 {m['macro_f1']:.4f}"
+            with open(os.path.join(self.log_dir, "eval_metrics.jsonl"), "a") as f:
+                f.write(json.dumps({"step": int(step), **m}) + "\n")
+        self.log(line)
 
     def flush(self) -> None:
         self.writer.flush()

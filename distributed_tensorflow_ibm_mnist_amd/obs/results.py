@@ -30,7 +30,10 @@ def read_label_file(path: Optional[str], n: int) -> List[str]:
 
 
 def writeClassificationResult(path: str, imagenames: Sequence, prediction: np.ndarray, ground_truth=None,
-                              prob_thresh: float = 0.5, label_file: Optional[str] = None) -> dict:
+                              prob_thresh: float = 0.5, label_file: Optional[str] = None,
+                              extra_summary: Optional[dict] = None) -> dict:
+    """``extra_summary``: further keys of the result's ``summary`` (the per-image rows, ``count``
+    and ``accuracy`` are what they are without it)."""
     prediction = np.asarray(prediction, dtype=np.float64)
     n, k = prediction.shape if prediction.ndim == 2 else (0, 10)
     names = read_label_file(label_file, k)
@@ -53,6 +56,8 @@ def writeClassificationResult(path: str, imagenames: Sequence, prediction: np.nd
     summary = {"count": n}
     if ground_truth is not None and n:
         summary["accuracy"] = float(np.mean([r["correct"] for r in rows]))
+    if extra_summary:
+        summary.update(extra_summary)
     out = {"summary": summary, "results": rows}
     os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
     jpath = path if path.endswith(".json") else path + ".json" if not os.path.splitext(path)[1] else path

@@ -318,3 +318,26 @@ def dropout_mask(step: torch.Tensor, seed: int, layer: int, rows: int, n: int, p
     out = torch.empty(rows, n, dtype=torch.uint8, device=step.device)
     kernels().dropout_mask(out, rows, n, step, seed, layer, p)
     return out
+
+
+def eval_metrics(logits: torch.Tensor, labels: Optional[torch.Tensor], n_classes: int, nb: Optional[int] = None,
+                 acc_i: Optional[torch.Tensor] = None, acc_f: Optional[torch.Tensor] = None,
+                 scratch: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None,
+                 temperature: float = 1.0, n_bins: int = 15):
+    """Confusion matrix, rank histogram, reliability bins and NLL / Brier sums of ``logits[:nb]``
+    (fp32 or bf16 ``[B, ld]``, ``n_classes`` real columns) ADDED to ``acc_i`` (int64) / ``acc_f``
+    (float64), laid out as ``kernels().eval_metrics_layout(n_classes, n_bins)`` says (zeroed ones
+    are made when none are given; ``obs/eval_metrics.py`` holds the definitions).  ``rows``: an
+    ``int32 [B, 4]`` tensor that receives ``(pred, rank, bin, bits of conf)`` of every row below
+    ``nb``.  Returns ``(acc_i, acc_f)``."""
+    K = kernels()
+    lay = K.eval_metrics_layout(n_classes, n_bins)
+    if acc_i is None:
+        acc_i = torch.zeros(lay["size_i"], dtype=torch.int64, device=logits.device)
+    if acc_f is None:
+        acc_f = torch.zeros(lay["size_f"], dtype=torch.float64, device=logits.device)
+    if scratch is None:
+        scratch = torch.empty(K.eval_metrics_scratch_size(n_bins), dtype=torch.float64, device=logits.device)
+    K.eval_metrics(logits, labels, logits.shape[0] if nb is None else nb, n_classes, acc_i, acc_f, scratch, rows,
+                   temperature, n_bins)
+    return acc_i, acc_f

@@ -1309,8 +1309,8 @@ class PSWorkerReplica:
     def read_stats(self):
         return self.net.read_stats()
 
-    def evaluate(self, max_examples=None):
-        return self.base.evaluate(max_examples)
+    def evaluate(self, max_examples=None, metrics=False):
+        return self.base.evaluate(max_examples, metrics=metrics)
 
     def inject_nan(self) -> None:
         self.base.inject_nan()

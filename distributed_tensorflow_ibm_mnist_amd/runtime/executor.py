@@ -928,9 +928,19 @@ class HipNet:
         self.update(grad_scale)
 
     # ------------------------------------------------------------------ eval
-    def eval_batch(self, nb: int, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Forward only on x0[:nb] / labels[:nb]; accumulates loss/correct into stats."""
+    def eval_batch(self, nb: int, stats: Optional[torch.Tensor] = None, metrics=None) -> torch.Tensor:
+        """Forward only on x0[:nb] / labels[:nb]; accumulates loss/correct into stats.
+        ``metrics``: an ``obs.eval_metrics.EvalAccumulator`` that also receives the batch.  The
+        head then runs layer by layer, so that the logits are stored (a fused head keeps them in
+        registers or writes them after the loss), and loss / correct come from the layered
+        softmax-CE: they may differ from the fused head's in the last bits."""
         st = self.eval_stats if stats is None else stats
+        if metrics is not None:
+            self.forward(nb, from_x0=True)
+            kernels().softmax_ce(self.logits, self.logits.shape[1], self.labels, nb, self.n_classes, 1.0, None,
+                                 self.logits.shape[1], st, None, self.ce_work)
+            metrics.add(self.logits, self.labels, nb)
+            return st
         self.forward(nb, from_x0=True, defer_head=True)
         if self._head_pending is not None:
             self._run_head(nb, 1.0, False, st)

@@ -400,11 +400,14 @@ class HipNetF32:
         self.backward()
         self.update(grad_scale)
 
-    def eval_batch(self, nb: int, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def eval_batch(self, nb: int, stats: Optional[torch.Tensor] = None, metrics=None) -> torch.Tensor:
+        """``metrics``: an ``obs.eval_metrics.EvalAccumulator`` that also receives the batch's logits."""
         st = self.eval_stats if stats is None else stats
         self.forward(nb)
         kernels().f32_softmax_ce(self.logits, self.logits.shape[1], self.labels, nb, self.n_classes, 1.0, None,
                                  self.logits.shape[1], st, None, self.ce_work)
+        if metrics is not None:
+            metrics.add(self.logits, self.labels, nb)
         return st
 
     def probs(self, nb: int) -> torch.Tensor:

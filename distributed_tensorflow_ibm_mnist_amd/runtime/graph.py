@@ -23,6 +23,7 @@ fails the watchdog ("operation not permitted when stream is capturing").
 """
 from __future__ import annotations
 
+import gc
 from typing import Callable
 
 import torch
@@ -38,6 +39,12 @@ class StepGraph:
                 fn()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        # Dead reference cycles go now, not during the capture: a Replica and its StepGraph form
+        # one (the graph holds the replica's bound step), so an abandoned replica's CUDAGraph is
+        # destroyed by the cycle collector whenever that happens to run, its destructor
+        # synchronises the device, and a synchronisation inside a capture aborts the process.
+        # torch.cuda.graph itself no longer collects before capturing.
+        gc.collect()
         self.graph = torch.cuda.CUDAGraph()
         import torch.distributed as dist
         mode = "thread_local" if dist.is_available() and dist.is_initialized() else "global"

@@ -252,13 +252,17 @@ class TorchNet:
         self.backward()
         self.update(grad_scale)
 
-    def eval_batch(self, nb: int, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def eval_batch(self, nb: int, stats: Optional[torch.Tensor] = None, metrics=None) -> torch.Tensor:
+        """``metrics``: an ``obs.eval_metrics.EvalAccumulator``; the batch's logits go to its host
+        reference (``obs/eval_metrics.py``), wherever this net lives."""
         st = self.eval_stats if stats is None else stats
         with torch.no_grad():
             logits = self.forward(nb, grad=False)
             lab = self.labels[:nb].long()
             st[0] += F.cross_entropy(logits, lab, reduction="sum")
             st[1] += _in_top1(logits, lab)
+            if metrics is not None:
+                metrics.add(logits.float().cpu(), self.labels[:nb].cpu(), nb)
         return st
 
     def probs(self, nb: int) -> torch.Tensor:

@@ -145,6 +145,7 @@ class Replica:
         self.use_graph = (use_graph and impl == "hip" and self.device.type == "cuda"
                           and (self.world == 1 or (dp_graph and dist.get_backend(group) == "nccl")))
         self._graph = None
+        self._eval_acc = None      # obs.eval_metrics.EvalAccumulator of evaluate(metrics=True), made on first use
         self.global_step = 0
         self.examples_per_step = batch * self.world
 
@@ -175,21 +176,39 @@ class Replica:
         # local replica's last step (no collective: hooks run on the chief only)
         return self.net.read_stats()
 
-    def evaluate(self, max_examples: Optional[int] = None) -> Dict[str, float]:
-        """Full (or capped) pass over the eval split; returns loss / accuracy."""
+    def evaluate(self, max_examples: Optional[int] = None, metrics: bool = False) -> Dict[str, float]:
+        """Full (or capped) pass over the eval split; returns loss / accuracy.
+        ``metrics``: the dict gains ``"metrics"``, ``obs.eval_metrics.derive`` of the pass's
+        accumulators (confusion matrix, top-k, NLL, Brier, ECE, per-class scores), computed on the
+        device where the logits are (one small copy for the whole pass).  ``loss`` / ``accuracy``
+        then come from the HIP executor's layered head, not its fused one: they may differ from
+        those of ``metrics=False`` in the last bits."""
         if self.eval_ds is None:
             return {"loss": float("nan"), "accuracy": float("nan")}
+        acc = None
+        if metrics:
+            from ..obs.eval_metrics import EvalAccumulator, derive
+            if self._eval_acc is None:
+                self._eval_acc = EvalAccumulator(self.device, self.net.n_classes)
+            acc = self._eval_acc
+            acc.zero()
         st = self.net.eval_stats
         st.zero_()
         n = 0
         for nb in eval_batches(self.eval_ds, self.net.x0, self.net.labels):
-            self.net.eval_batch(nb, st)
+            if acc is None:
+                self.net.eval_batch(nb, st)
+            else:
+                self.net.eval_batch(nb, st, metrics=acc)
             n += nb
             if max_examples and n >= max_examples:
                 break
         # local pass (no collective, so chief-only hooks can call it safely)
         v = (st[:2] / max(n, 1)).tolist()
-        return {"loss": v[0], "accuracy": v[1]}
+        out = {"loss": v[0], "accuracy": v[1]}
+        if acc is not None:
+            out["metrics"] = derive(acc.result())
+        return out
 
     def inject_nan(self) -> None:
         """Fault injection: poison params[0], the first layer's first weight.  On the torch path

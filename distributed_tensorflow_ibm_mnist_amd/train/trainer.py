@@ -164,7 +164,8 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
         from ..obs.monitor import Monitor
         monitor = Monitor(os.path.join(FLAGS.train_dir, "log"), test_interval, max_steps, replica,
                           eval_examples=FLAGS.eval_examples, log=log,
-                          device_summaries=bool(getattr(FLAGS, "monitor_device", 0)))
+                          device_summaries=bool(getattr(FLAGS, "monitor_device", 0)),
+                          eval_metrics=bool(getattr(FLAGS, "eval_metrics", 0)))
         monitor.register_reference_summaries()
 
     # main.py:137-138; the NaN flag is checked asynchronously every N steps

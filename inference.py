@@ -46,6 +46,12 @@ flags.DEFINE_boolean("per_image_standardization", False, "reference preprocessin
 flags.DEFINE_string("impl", "auto", "hip | torch | auto")
 flags.DEFINE_string("precision", "bf16", "HIP compute precision: bf16 | fp32 (the reference's tf.float32)")
 flags.DEFINE_integer("batch_size", 128, "inference batch (inference.py:34)")
+flags.DEFINE_integer("eval_metrics", 0, "1: with --validate the result's summary gains 'metrics' (confusion matrix, "
+                     "top-k, NLL, Brier, ECE / MCE, per-class scores; on the GPU for --impl=hip) and 'temperature'; "
+                     "in image mode it gains 'predicted_counts'.  0: nothing is added")
+flags.DEFINE_float("temperature", 1.0, "softmax temperature of the reported metrics (--eval_metrics)")
+flags.DEFINE_boolean("fit_temperature", False, "with --validate: fit the temperature that minimises the split's NLL, "
+                     "report the metrics at it ('metrics_T1': at T = 1); implies --eval_metrics=1")
 
 BATCH_SIZE = 128
 IMAGE_SIZE = 28
@@ -116,6 +122,17 @@ def predict(FLAGS):
     from distributed_tensorflow_ibm_mnist_amd.runtime.params import OptConfig
     net = build_net(impl, spec, B, dev, params, OptConfig(), FLAGS.precision)
 
+    # --eval_metrics: the logits probs() leaves behind go to the metrics kernel (the host reference
+    # on a CPU executor) batch by batch; --fit_temperature also keeps them, where they are
+    fit = bool(FLAGS.fit_temperature)
+    if fit and not FLAGS.validate:
+        raise SystemExit("--fit_temperature needs --validate (labels)")
+    acc, kept = None, []
+    if FLAGS.eval_metrics or fit:
+        from distributed_tensorflow_ibm_mnist_amd.obs import eval_metrics as em
+        acc = em.EvalAccumulator(dev, spec.num_classes, temperature=1.0 if fit else FLAGS.temperature)
+        lab_all = torch.from_numpy(np.asarray(labels).astype(np.int32)).to(dev)
+
     start = time.time()
     probs = []
     for s in range(0, len(x), B):                                              # inference.py:94-101
@@ -123,16 +140,34 @@ def predict(FLAGS):
         xb = torch.from_numpy(x[s:s + nb]).to(dev)
         net.x0.view(-1)[: xb.numel()].copy_(xb.reshape(-1).to(net.x0.dtype))
         probs.append(net.probs(nb).float().cpu().numpy()[:, : spec.num_classes])
+        if acc is not None:
+            net.labels[:nb].copy_(lab_all[s:s + nb])
+            logits = net.logits if hasattr(net, "logits") else net._logits
+            acc.add(logits, net.labels, nb)
+            if fit:
+                kept.append(logits[:nb].clone())
     prediction = np.concatenate(probs) if probs else np.zeros((0, spec.num_classes), np.float32)
     print("Predictions are Finished in %.2f s." % (time.time() - start))       # inference.py:102
     out_path = os.path.join(FLAGS.output_dir, FLAGS.output_file or "inference_result.json")
+    extra = None
+    if acc is not None and FLAGS.validate:
+        extra = {"metrics": em.derive(acc.result()), "temperature": acc.temperature}
+        if fit and kept:
+            all_logits = torch.cat(kept)
+            T = em.fit_temperature(all_logits, lab_all, spec.num_classes)
+            print("fitted temperature: %.4f" % T)
+            at_t = em.EvalAccumulator(dev, spec.num_classes, temperature=T)
+            at_t.add(all_logits, lab_all)
+            extra = {"metrics": em.derive(at_t.result()), "temperature": T, "metrics_T1": extra["metrics"]}
+    elif acc is not None:
+        extra = {"predicted_counts": [int(v) for v in acc.result()["confusion"][spec.num_classes]]}
     if FLAGS.validate:
-        res = writeClassificationResult(out_path, names, prediction, ground_truth=labels)
+        res = writeClassificationResult(out_path, names, prediction, ground_truth=labels, extra_summary=extra)
         print("validation accuracy: %.4f over %d images" % (res["summary"].get("accuracy", float("nan")),
                                                             len(names)))
     else:
         writeClassificationResult(out_path, names, prediction, prob_thresh=FLAGS.prob_thresh,
-                                  label_file=FLAGS.label_file)
+                                  label_file=FLAGS.label_file, extra_summary=extra)
     return prediction
 
 

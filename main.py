@@ -116,6 +116,10 @@ flags.DEFINE_integer("eval_examples", 10000, "examples per test-summary evaluati
 flags.DEFINE_integer("monitor_device", 0, "1: the chief's train summaries (histograms, norms, gw_ratio) are reduced "
                      "on the GPU and only bucket counts and moments are copied to the host; 0: host numpy. CPU "
                      "executors always use the host path")
+flags.DEFINE_integer("eval_metrics", 0, "1: every test summary also reports top-2 / top-3 accuracy, NLL, Brier score, "
+                     "ECE / MCE, macro-F1 and per-class recall / precision (computed on the GPU for --impl=hip, by "
+                     "the host reference otherwise) and appends a line to <train_dir>/log/eval_metrics.jsonl; 0: "
+                     "loss and accuracy alone")
 flags.DEFINE_string("ps_backend", "", "PS-mode data plane: '' (GPU: shm for PS shards up to 1 M parameters, e.g. "
                     "LeNet-5, ipc above, e.g. the reference CNN; CPU: host) | shm (CPU parameter server "
                     "serving a shared-memory segment natively; one host) | ipc (xGMI peer copies into a GPU PS) | "
