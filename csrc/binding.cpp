@@ -586,7 +586,7 @@ int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t 
   }
   float* wk = nullptr;
   if (work.has_value() && work->defined()) {
-    check(*work, at::kFloat, 4 * 1024 + 1, "work");
+    check(*work, at::kFloat, mnistx::CE_WORK_FLOATS, "work");
     wk = P<float>(*work);
   }
   float* db = nullptr;
@@ -630,7 +630,7 @@ void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t
   for (const Tensor* t : {&x, &w5t, &logits})
     TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "ce_tail: operands must be 16-byte aligned");
   const bool has_work = work.has_value() && work->defined();
-  if (has_work) check(*work, at::kFloat, 4 * 1024 + 1, "work");
+  if (has_work) check(*work, at::kFloat, mnistx::CE_WORK_FLOATS, "work");
   mnistx::bf16_t *pdl = nullptr, *pdx = nullptr;
   if (dl.has_value() && dl->defined()) {
     TORCH_CHECK(dx.has_value() && dx->defined(), "ce_tail: dl needs dx");
@@ -649,10 +649,10 @@ void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t
   }
   TORCH_CHECK(eps == 0.f || pdl != nullptr, "ce_tail: label_smoothing is a training quantity and needs dl");
   TORCH_CHECK(mx.labels2 == nullptr || pdl != nullptr, "ce_tail: labels2 / lam are training quantities and need dl");
-  hip_ok(mnistx::ce_tail(BF(x), BF(w5t), P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale,
-                         P<float>(logits), pdl, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr, cur_stream(),
-                         defer_stats ? 1 : 0, db, eps, mx.labels2, mx.lam),
-         "ce_tail");
+  const mnistx::TailArgs a{BF(x), BF(w5t), P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale,
+                           P<float>(logits), pdl, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr,
+                           defer_stats ? 1 : 0, db};
+  hip_ok(mnistx::ce_tail(a, cur_stream(), eps, mx.labels2, mx.lam), "ce_tail");
 }
 
 // The dropout arguments of a binding, validated (ValueError): the drop rate p (finite, 0 <= p < 1) as
@@ -712,7 +712,7 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
   check(logits, at::kFloat, nb * 16, "logits");
   check(stats, at::kFloat, 8, "stats");
   const bool has_work = work.has_value() && work->defined();   // none: order-dependent atomics
-  if (has_work) check(*work, at::kFloat, 4 * 1024 + 1, "work");
+  if (has_work) check(*work, at::kFloat, mnistx::CE_WORK_FLOATS, "work");
   for (const Tensor* t : {&x, &w3t, &w4t, &w5t, &h3, &h4, &logits})
     TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "mlp_head: operands must be 16-byte aligned");
   mnistx::bf16_t *pdl = nullptr, *pdh4 = nullptr, *pdh3 = nullptr, *pdx = nullptr;
@@ -738,12 +738,11 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
   TORCH_CHECK(eps == 0.f || pdl != nullptr, "mlp_head: label_smoothing is a training quantity and needs dl");
   TORCH_CHECK(hd.step == nullptr || pdl != nullptr, "mlp_head: dropout is a training quantity and needs dl");
   TORCH_CHECK(mx.labels2 == nullptr || pdl != nullptr, "mlp_head: labels2 / lam are training quantities and need dl");
-  hip_ok(mnistx::mlp_head(BF(x), BF(w3t), P<const float>(b3), (int)n1, BF(w4t), P<const float>(b4), (int)n2, BF(w5t),
-                          P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale, BFm(h3),
-                          BFm(h4), P<float>(logits), pdl, pdh4, pdh3, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr,
-                          cur_stream(), (defer_stats && has_work) ? 1 : 0, db, eps, hd.step ? &hd : nullptr, mx.labels2,
-                          mx.lam),
-         "mlp_head");
+  const mnistx::HeadArgs a{BF(x), BF(w3t), P<const float>(b3), (int)n1, BF(w4t), P<const float>(b4), (int)n2, BF(w5t),
+                           P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale, BFm(h3),
+                           BFm(h4), P<float>(logits), pdl, pdh4, pdh3, pdx, P<float>(stats),
+                           has_work ? P<float>(*work) : nullptr, (defer_stats && has_work) ? 1 : 0, db};
+  hip_ok(mnistx::mlp_head(a, cur_stream(), eps, hd.step ? &hd : nullptr, mx.labels2, mx.lam), "mlp_head");
 }
 
 // stand-alone dropout (dropout.hip), in place on x [nb, ld] bf16 with n real columns
@@ -1337,7 +1336,7 @@ mnistx::FinArgs prep_fin(Tensor step, Tensor stats, optional<Tensor> l2, optiona
   f.l2base = (int)nw;
   if (ce_nblk > 0) {
     TORCH_CHECK(ce_work.has_value() && ce_work->defined() && ce_nblk <= 1024, "ce_work needed for ce_nblk > 0");
-    check(*ce_work, at::kFloat, 4 * 1024 + 1, "ce_work");
+    check(*ce_work, at::kFloat, mnistx::CE_WORK_FLOATS, "ce_work");
     f.ce_work = P<const float>(*ce_work);
     f.ce_nblk = (int)ce_nblk;
   }
@@ -1875,7 +1874,7 @@ void f32_softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t
   }
   float* wk = nullptr;
   if (work.has_value() && work->defined()) {
-    check(*work, at::kFloat, 4 * 1024 + 1, "work");
+    check(*work, at::kFloat, mnistx::CE_WORK_FLOATS, "work");
     wk = P<float>(*work);
   }
   TORCH_CHECK(eps == 0.f || lab != nullptr, "f32_softmax_ce: label_smoothing needs labels");

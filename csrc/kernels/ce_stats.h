@@ -6,61 +6,92 @@
 // results across runs and between hipGraph replay and eager execution.
 #pragma once
 #include "common.h"
+#include "launchers.h"
 
 #include <type_traits>
 
-constexpr int CE_MAXB = 1024;  // max blocks per launch (work holds 4 floats per block + ticket)
+using mnistx::CE_MAXB;   // max blocks per launch (work holds 4 floats per block + ticket)
 
-// Label smoothing.  The softmax-CE kernels take a compile-time SMOOTH switch; the smoothed
-// instantiation has ONE more trailing kernel argument, eps (a `float` argument pack, empty in the
-// plain instantiation, whose arguments and code therefore stay what they were).  With
-// on = 1 - eps and off = eps / NC (NC = the real class count):
-//   loss = log(se) - on * (l_y - mx) - off * sum_{c < NC} (l_c - mx)
-//   dl_c = (p_c - on * [c == y] - off) * scale
-// The class sum is over the differences, which stay finite for |l_c - mx| <= 1e37.
-template <typename... T>
-DEV float smooth_eps(T... eps) {
-  static_assert(sizeof...(T) <= 1, "one eps at most");
-  if constexpr (sizeof...(T) == 0) return 0.f;
-  else return (eps + ...);
-}
+// The label target of the softmax-CE kernels, one view of their trailing argument pack.  The pack is
+// [eps] [labels2, lam] [HeadDrop]; what it holds is read off its types, so the plain instantiation has
+// no trailing argument and keeps the arguments and the code it always had.
+//   SMOOTH (eps): label smoothing.  With on = 1 - eps and off = eps / NC (NC = the real class count):
+//     loss = log(se) - on * (l_y - mx) - off * sum_{c < NC} (l_c - mx)
+//     dl_c = (p_c - on * [c == y] - off) * scale
+//   The class sum is over the differences, which stay finite for |l_c - mx| <= 1e37.
+//   MIX (eps, which may be 0, then labels2 and lam): two labels per row (mixup / CutMix, mix.hip).  With
+//   ya = labels[m], yb = labels2[m], lam = lam[m] and om = 1 - lam:
+//     loss = log(se) - on * (lam (l_ya - mx) + om (l_yb - mx)) - off * sum_{c < NC} (l_c - mx)
+//     dl_c = (p_c - on * (lam [c == ya] + om [c == yb]) - off) * scale
+//   A row with lam == 1 drops the yb term by a select, never by a product with 0: an infinite l_yb leaves
+//   such a row finite.  eps = 0 (off == 0) leaves the class sum out by a select too: a -inf logit in a
+//   class no label names makes it -inf, and 0 * inf is NaN.  lam + om is exactly 1 for lam in [0.5, 1],
+//   so ya == yb gives `on` at that class.  The top-1 count stays l_ya >= mx: ya is the dominant label.
+//   DROP (a HeadDrop closes the pack; mlp_head_k alone): dropout on the hidden layers (dropout_rng.h).
+// A kernel builds one CeTarget from (NC, eps...) and one Row per batch row (the second label and the
+// weight are loaded there, once), fills in what the row's loss reads beside da = l_ya - mx and lse =
+// log(se) -- db = l_yb - mx where the Row has it, the class sum sd likewise -- and asks for the row's
+// loss and for the target q of a class.  The plain Row is the label alone: a plain kernel declares
+// nothing it does not use (a dead declaration is enough to change its register allocation).
+struct CeRow { int ya; };
+struct CeRowSmooth { int ya; float sd; };
+struct CeRowMix { int ya, yb; float lam, om, db, sd; };
 
-// Two labels per row (mixup / CutMix, mix.hip).  The MIX form of the same kernels is read off the
-// pack's types: (eps, const int32_t* labels2, const float* lam [, ...]) instead of (eps); eps is
-// always there and may be 0, so mixing and smoothing share one instantiation per kernel.  With
-// ya = labels[m], yb = labels2[m], lam = lam[m] and om = 1 - lam:
-//   loss = log(se) - on * (lam (l_ya - mx) + om (l_yb - mx)) - off * sum_{c < NC} (l_c - mx)
-//   dl_c = (p_c - on * (lam [c == ya] + om [c == yb]) - off) * scale
-// A row with lam == 1 drops the yb term by a select (mix_om, mix_logit), never by a product with 0:
-// an infinite l_yb leaves such a row finite.  lam + om is exactly 1 for lam in [0.5, 1], so ya == yb
-// gives `on` at that class.  The top-1 count stays l_ya >= mx: ya is the dominant label.
-template <typename... T>
-constexpr bool pack_has_mix = (std::is_same_v<T, const float*> || ...);
-template <typename... R>
-DEV float mix_eps(float e, const int32_t*, const float*, R...) { return e; }
-template <typename... R>
-DEV const int32_t* mix_labels2(float, const int32_t* l2, const float*, R...) { return l2; }
-template <typename... R>
-DEV const float* mix_lam(float, const int32_t*, const float* lm, R...) { return lm; }
-// labels2[m] / lam[m]; the fused heads pass min(m, nb - 1), as their X loads do (a row past the batch
-// is never stored or counted), so the loads sit under no branch and repeated calls merge into one
-template <typename... A>
-DEV int mix_row_label(int64_t m, A... a) { return mix_labels2(a...)[m]; }
-template <typename... A>
-DEV float mix_row_lam(int64_t m, A... a) { return mix_lam(a...)[m]; }
-DEV float mix_om(float lam) { return lam < 1.f ? 1.f - lam : 0.f; }
-// lam (l_ya - mx) + om (l_yb - mx) from da = l_ya - mx, db = l_yb - mx
-DEV float mix_logit(float lam, float da, float db) { return lam < 1.f ? fmaf(lam, da, (1.f - lam) * db) : da; }
-// the loss from tl = mix_logit(..), the class sum sd and lse = log(se).  eps = 0 (off == 0) leaves the
-// class sum out by a select: a -inf logit in a class no label names makes sd -inf, and 0 * inf is NaN
-DEV float mix_ce(float on, float off, float tl, float sd, float lse) {
-  const float a = fmaf(-on, tl, lse);
-  return off != 0.f ? fmaf(-off, sd, a) : a;
-}
-// the target of class c: on * (lam [c == ya] + om [c == yb]) + off
-DEV float mix_target(int c, int ya, int yb, float lam, float om, float on, float off) {
-  return fmaf(on, (c == ya ? lam : 0.f) + (c == yb ? om : 0.f), off);
-}
+template <typename... P>
+struct CeTarget {
+  static constexpr bool SMOOTH = (std::is_same_v<P, float> || ...);
+  static constexpr bool MIX = (std::is_same_v<P, const float*> || ...);
+  static constexpr bool DROP = (std::is_same_v<P, mnistx::HeadDrop> || ...);
+  static_assert(sizeof...(P) == (SMOOTH ? 1 : 0) + (MIX ? 2 : 0) + (DROP ? 1 : 0) && (SMOOTH || !MIX),
+                "the pack is [eps] [labels2, lam] [HeadDrop]; labels2 and lam come with eps");
+  static constexpr bool NEEDS_DB = MIX, NEEDS_SD = SMOOTH;   // the Row has db / sd for the kernel to fill in
+  using Row = std::conditional_t<MIX, CeRowMix, std::conditional_t<SMOOTH, CeRowSmooth, CeRow>>;
+
+  float on = 1.f, off = 0.f;
+  const int32_t* labels2 = nullptr;
+  const float* lam = nullptr;
+  const mnistx::HeadDrop* drop = nullptr;
+
+  DEV CeTarget(int nc, const P&... p) { (take(nc, p), ...); }
+
+  // The target of row m with first label ya.  The fused heads pass min(m, nb - 1), as their X loads do
+  // (a row past the batch is never stored or counted), so the two loads sit under no branch.
+  DEV Row row(int ya, int64_t m) const {
+    if constexpr (MIX) {
+      const float lm = lam[m];
+      return Row{ya, labels2[m], lm, lm < 1.f ? 1.f - lm : 0.f, 0.f, 0.f};
+    } else if constexpr (SMOOTH) {
+      return Row{ya, 0.f};
+    } else {
+      return Row{ya};
+    }
+  }
+  DEV float loss(const Row& r, float da, float lse) const {
+    if constexpr (MIX) {
+      const float tl = r.lam < 1.f ? fmaf(r.lam, da, (1.f - r.lam) * r.db) : da;
+      const float a = fmaf(-on, tl, lse);
+      return off != 0.f ? fmaf(-off, r.sd, a) : a;
+    } else if constexpr (SMOOTH) {
+      return fmaf(-off, r.sd, fmaf(-on, da, lse));
+    } else {
+      return -(da - lse);
+    }
+  }
+  DEV float q(const Row& r, int c) const {
+    if constexpr (MIX) return fmaf(on, (c == r.ya ? r.lam : 0.f) + (c == r.yb ? r.om : 0.f), off);
+    else if constexpr (SMOOTH) return c == r.ya ? on + off : off;
+    else return c == r.ya ? 1.f : 0.f;
+  }
+
+ private:
+  DEV void take(int nc, float eps) {
+    off = eps / (float)nc;
+    on = 1.f - eps;
+  }
+  DEV void take(int, const int32_t* l2) { labels2 = l2; }
+  DEV void take(int, const float* lm) { lam = lm; }
+  DEV void take(int, const mnistx::HeadDrop& d) { drop = &d; }
+};
 
 // Every thread of the block must call this (it synchronises the block).
 // With work == nullptr each block adds its partial atomically (order-dependent).

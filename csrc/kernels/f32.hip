@@ -416,19 +416,16 @@ __global__ __launch_bounds__(256) void lrn_f32_bwd_k(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------- softmax cross-entropy, fp32 gradient
-// SMOOTH: label smoothing (ce_stats.h), eps as the one member of the trailing argument pack.
+// The label target (plain, or SMOOTH: eps) is the trailing pack's CeTarget (ce_stats.h).
 template <bool SMOOTH = false, typename... EPS>
 __global__ __launch_bounds__(256) void softmax_ce_f32_k(const float* __restrict__ logits, int ldl,
                                                         const int32_t* __restrict__ labels, int B, int NC,
                                                         float scale, float* __restrict__ dl, int ldd,
                                                         float* __restrict__ stats, float* __restrict__ probs,
                                                         float* __restrict__ work, EPS... eps) {
-  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0), "the smoothed instantiation takes eps");
-  float sm_on = 1.f, sm_off = 0.f;
-  if constexpr (SMOOTH) {
-    sm_on = 1.f - smooth_eps(eps...);
-    sm_off = smooth_eps(eps...) / (float)NC;
-  }
+  using TG = CeTarget<EPS...>;
+  static_assert(SMOOTH == TG::SMOOTH && !TG::MIX && !TG::DROP, "the smoothed instantiation takes eps; no other form");
+  const TG tg(NC, eps...);
   float loss = 0.f, corr = 0.f, bad = 0.f;
   for (int row = blockIdx.x * 256 + threadIdx.x; row < B; row += gridDim.x * 256) {
     const float* l = logits + (int64_t)row * ldl;
@@ -438,28 +435,19 @@ __global__ __launch_bounds__(256) void softmax_ce_f32_k(const float* __restrict_
     for (int c = 0; c < NC; ++c) se += expf(l[c] - mx);
     const float inv = 1.f / se;
     const int lab = labels ? labels[row] : -1;
+    typename TG::Row tr = tg.row(lab, row);
     if (labels) {
       const float ll = l[lab];
-      float lo;
-      if constexpr (SMOOTH) {
-        float sd = 0.f;
-        for (int c = 0; c < NC; ++c) sd += l[c] - mx;
-        lo = fmaf(-sm_off, sd, fmaf(-sm_on, ll - mx, logf(se)));
-      } else {
-        lo = -(ll - mx - logf(se));
-      }
+      if constexpr (TG::NEEDS_SD)
+        for (int c = 0; c < NC; ++c) tr.sd += l[c] - mx;
+      const float lo = tg.loss(tr, ll - mx, logf(se));
       loss += lo;
       corr += ll >= mx ? 1.f : 0.f;
       if (!isfinite(lo)) bad = 1.f;
     }
     if (dl)
-      for (int c = 0; c < ldd; ++c) {
-        if constexpr (SMOOTH)
-          dl[(int64_t)row * ldd + c] =
-              c < NC ? (expf(l[c] - mx) * inv - (c == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
-        else
-          dl[(int64_t)row * ldd + c] = c < NC ? (expf(l[c] - mx) * inv - (c == lab ? 1.f : 0.f)) * scale : 0.f;
-      }
+      for (int c = 0; c < ldd; ++c)
+        dl[(int64_t)row * ldd + c] = c < NC ? (expf(l[c] - mx) * inv - tg.q(tr, c)) * scale : 0.f;
     if (probs)
       for (int c = 0; c < NC; ++c) probs[(int64_t)row * NC + c] = expf(l[c] - mx) * inv;
   }

@@ -35,6 +35,11 @@ inline int reserve_cut(int resident, int per_cu) {
 hipError_t clock_mark(uint64_t* out, int slot, hipStream_t st);
 hipError_t coresidency_probe(uint64_t* out, int blocks, int threads, int lds_bytes, int spin_ticks, hipStream_t st);
 
+// The CE statistics work buffer (ce_stats.h): 4 floats per block of a launch, at most CE_MAXB blocks,
+// and the ticket counter behind them
+constexpr int CE_MAXB = 1024;
+constexpr int64_t CE_WORK_FLOATS = 4 * CE_MAXB + 1;
+
 enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_SLAB = 2 };
 
 struct GemmEpi {
@@ -281,8 +286,8 @@ hipError_t lrn_pool_fwd(const bf16_t* x, int Nb, int H, int W, int C, int r, flo
 void lrn_set_packed(int on);
 hipError_t lrn_pool_bwd(const bf16_t* x, const bf16_t* dP, const uint8_t* arg, int Nb, int H, int W, int C, int r,
                         float bias, float alpha, float beta, int relu_mask, bf16_t* dx, hipStream_t st);
-// work (optional): >= 4*1024+1 floats, zero-initialised once; makes the loss /
-// accuracy sums deterministic (per-block partials combined in block order)
+// work (optional): >= CE_WORK_FLOATS floats, zero-initialised once; makes the loss /
+// accuracy sums deterministic (per-block partials combined in block order, ce_stats.h)
 // defer_blocks (optional out): with it, the row kernel writes per-block partials only and
 // reports its block count there (0 when the fallback kernel ran: plain atomics); the
 // caller's finalize_step combines them (ce_stats.h defer)
@@ -315,53 +320,65 @@ struct HeadDrop {
   float inv_keep;
 };
 bool mlp_head_supported(int d0, int ld1, int ld2, int ld3, int n1, int n2, int nc, int B);
-// w3t / w4t / w5t: zero-padded W^T copies [128][416], [96][128], [16][96].
-hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t, const float* b4,
-                    int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
-                    bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
-                    float* stats, float* work, hipStream_t st, int defer_stats = 0, float* dbias = nullptr,
-                    float label_smoothing = 0.f, const HeadDrop* drop = nullptr, const int32_t* labels2 = nullptr,
-                    const float* lam = nullptr);
+// The operands of mlp_head, in the order of mlp_head_k's arguments.  w3t / w4t / w5t: zero-padded W^T
+// copies [128][416], [96][128], [16][96].
+struct HeadArgs {
+  const bf16_t *x, *w3t;
+  const float* b3;
+  int n1;
+  const bf16_t* w4t;
+  const float* b4;
+  int n2;
+  const bf16_t* w5t;
+  const float* b5;
+  int nc;
+  const int32_t* labels;
+  int nb;
+  float scale;
+  bf16_t *h3, *h4;
+  float* logits;
+  bf16_t *dl, *dh4, *dh3, *dx;
+  float *stats, *work;
+  int defer_stats;
+  float* dbias;
+};
+hipError_t mlp_head(const HeadArgs& a, hipStream_t st, float label_smoothing = 0.f, const HeadDrop* drop = nullptr,
+                    const int32_t* labels2 = nullptr, const float* lam = nullptr);
 // blocks of one mlp_head launch (its per-block CE partials when defer_stats is set)
 int mlp_head_blocks(int nb);
 // the reference CNN's softmax_linear (192 -> nc <= 16) + softmax CE + its data gradient (masked by
 // x > 0) in one launch; w5t = W^T [16][192] (the optimizer's transposed copy); dbias: fp32 per-block
-// column sums [ce_tail_blocks][16]
+// column sums [ce_tail_blocks][16].  TailArgs: the operands in the order of ce_tail_k's arguments.
 bool ce_tail_supported(int d0, int nc, int B);
 int ce_tail_blocks(int nb);
-hipError_t ce_tail(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
-                   float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                   int defer_stats, float* dbias, float label_smoothing = 0.f, const int32_t* labels2 = nullptr,
-                   const float* lam = nullptr);
-// the smoothed instantiations (mlp_head_smooth.hip), which mlp_head / ce_tail call for
-// label_smoothing != 0: the gradient form only (dl required)
 int ce_tail_nw(int nb);
-hipError_t ce_tail_smooth(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
-                          float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work,
-                          hipStream_t st, int defer_stats, float* dbias, float label_smoothing);
-hipError_t mlp_head_smooth(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
-                           const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
-                           int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
-                           bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
-                           float* dbias, float label_smoothing);
-// the dropped instantiations (mlp_head_drop.hip), with label smoothing or without
-hipError_t mlp_head_drop(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
-                         const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
-                         int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
-                         bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
-                         float* dbias, float label_smoothing, const HeadDrop& drop);
-// the two-label instantiations (mlp_head_mix.hip; mixup / CutMix), which mlp_head / ce_tail call when
-// labels2 and lam are given: the gradient form only; label_smoothing as it is (0 allowed); drop may be
-// nullptr
-hipError_t ce_tail_mix(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
-                       float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                       int defer_stats, float* dbias, float label_smoothing, const int32_t* labels2, const float* lam);
-hipError_t mlp_head_mix(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
-                        const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
-                        int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
-                        bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
-                        float* dbias, float label_smoothing, const int32_t* labels2, const float* lam,
-                        const HeadDrop* drop);
+struct TailArgs {
+  const bf16_t *x, *w5t;
+  const float* b5;
+  int nc;
+  const int32_t* labels;
+  int nb;
+  float scale;
+  float* logits;
+  bf16_t *dl, *dx;
+  float *stats, *work;
+  int defer_stats;
+  float* dbias;
+};
+hipError_t ce_tail(const TailArgs& a, hipStream_t st, float label_smoothing = 0.f, const int32_t* labels2 = nullptr,
+                   const float* lam = nullptr);
+// What mlp_head / ce_tail call for the other label targets, each a translation unit of its own (the note
+// in mlp_head.hip); all are the gradient form only (dl required).  mlp_head_smooth.hip: label_smoothing != 0
+hipError_t ce_tail_smooth(const TailArgs& a, hipStream_t st, float label_smoothing);
+hipError_t mlp_head_smooth(const HeadArgs& a, hipStream_t st, float label_smoothing);
+// mlp_head_drop.hip: dropout, with label smoothing or without
+hipError_t mlp_head_drop(const HeadArgs& a, hipStream_t st, float label_smoothing, const HeadDrop& drop);
+// mlp_head_mix.hip: labels2 and lam given (mixup / CutMix); label_smoothing as it is (0 allowed); drop may
+// be nullptr
+hipError_t ce_tail_mix(const TailArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2,
+                       const float* lam);
+hipError_t mlp_head_mix(const HeadArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2,
+                        const float* lam, const HeadDrop* drop);
 // Stand-alone dropout (dropout.hip) on a [nb, ld] bf16 buffer with n <= ld real columns, in place:
 // x = keep ? bf16(x * inv_keep) : +0, the keep bits of (seed, *step, layer) from dropout_rng.h.
 // Forward (on the activation) and backward (on the gradient: the bits are recomputed) are the same

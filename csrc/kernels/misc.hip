@@ -526,23 +526,14 @@ __global__ __launch_bounds__(TPB) void lrn_pool14_bwd_k(const bf16_t* __restrict
 
 // ------------------------------------------------------------------ K8 softmax cross-entropy
 // stats[0] += sum(-log p[label]) ; stats[1] += #(logit[label] == max) ; stats[2] = 1 if non-finite.
-// SMOOTH: label smoothing (ce_stats.h), eps as the one member of the trailing argument pack.
-// MIX (the pack is eps, labels2, lam): two labels and a weight per row (ce_stats.h).
+// The label target (plain; SMOOTH: eps; two labels: eps, labels2, lam) is the trailing pack's CeTarget (ce_stats.h).
 template <bool SMOOTH = false, typename... EPS>
 __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ labels, int B,
                              int NC, float scale, bf16_t* __restrict__ dl, int ldd, float* __restrict__ stats,
                              float* __restrict__ probs, EPS... eps) {
-  constexpr bool MIX = pack_has_mix<EPS...>;
-  static_assert(sizeof...(EPS) == (MIX ? 3 : SMOOTH ? 1 : 0) && (SMOOTH || !MIX),
-                "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
-  float sm_on = 1.f, sm_off = 0.f;
-  if constexpr (MIX) {
-    sm_on = 1.f - mix_eps(eps...);
-    sm_off = mix_eps(eps...) / (float)NC;
-  } else if constexpr (SMOOTH) {
-    sm_on = 1.f - smooth_eps(eps...);
-    sm_off = smooth_eps(eps...) / (float)NC;
-  }
+  using TG = CeTarget<EPS...>;
+  static_assert(SMOOTH == TG::SMOOTH && !TG::DROP, "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
+  const TG tg(NC, eps...);
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   float loss = 0.f, corr = 0.f;
   int bad = 0;
@@ -554,21 +545,13 @@ __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const in
     for (int c = 0; c < NC; ++c) se += __expf(l[c] - mx);
     const float inv = 1.f / se;
     const int lab = labels ? labels[row] : -1;
+    typename TG::Row tr = tg.row(lab, row);
     if (labels) {
       const float ll = l[lab];
-      if constexpr (MIX) {
-        const int lab2 = mix_labels2(eps...)[row];
-        const float lm = mix_lam(eps...)[row];
-        float sd = 0.f;
-        for (int c = 0; c < NC; ++c) sd += l[c] - mx;
-        loss = mix_ce(sm_on, sm_off, mix_logit(lm, ll - mx, l[lab2] - mx), sd, __logf(se));
-      } else if constexpr (SMOOTH) {
-        float sd = 0.f;
-        for (int c = 0; c < NC; ++c) sd += l[c] - mx;
-        loss = fmaf(-sm_off, sd, fmaf(-sm_on, ll - mx, __logf(se)));
-      } else {
-        loss = -(ll - mx - __logf(se));
-      }
+      if constexpr (TG::NEEDS_DB) tr.db = l[tr.yb] - mx;
+      if constexpr (TG::NEEDS_SD)
+        for (int c = 0; c < NC; ++c) tr.sd += l[c] - mx;
+      loss = tg.loss(tr, ll - mx, __logf(se));
       corr = (ll >= mx) ? 1.f : 0.f;
       if (!isfinite(loss)) bad = 1;
     }
@@ -576,15 +559,7 @@ __global__ void softmax_ce_k(const float* __restrict__ logits, int ldl, const in
       bf16_t* d = dl + (int64_t)row * ldd;
       for (int c = 0; c < ldd; ++c) {
         float g = 0.f;
-        if constexpr (MIX) {
-          const int lab2 = mix_labels2(eps...)[row];
-          const float lm = mix_lam(eps...)[row];
-          if (c < NC) g = (__expf(l[c] - mx) * inv - mix_target(c, lab, lab2, lm, mix_om(lm), sm_on, sm_off)) * scale;
-        } else if constexpr (SMOOTH) {
-          if (c < NC) g = (__expf(l[c] - mx) * inv - (c == lab ? sm_on + sm_off : sm_off)) * scale;
-        } else {
-          if (c < NC) g = (__expf(l[c] - mx) * inv - (c == lab ? 1.f : 0.f)) * scale;
-        }
+        if (c < NC) g = (__expf(l[c] - mx) * inv - tg.q(tr, c)) * scale;
         d[c] = f2bf(g);
       }
     }
@@ -615,17 +590,9 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
                                                          float* __restrict__ stats, float* __restrict__ probs,
                                                          float* __restrict__ work, int defer_stats,
                                                          float* __restrict__ dbias, EPS... eps) {
-  constexpr bool MIX = pack_has_mix<EPS...>;
-  static_assert(sizeof...(EPS) == (MIX ? 3 : SMOOTH ? 1 : 0) && (SMOOTH || !MIX),
-                "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
-  float sm_on = 1.f, sm_off = 0.f;
-  if constexpr (MIX) {
-    sm_on = 1.f - mix_eps(eps...);
-    sm_off = mix_eps(eps...) / (float)NC;
-  } else if constexpr (SMOOTH) {
-    sm_on = 1.f - smooth_eps(eps...);
-    sm_off = smooth_eps(eps...) / (float)NC;
-  }
+  using TG = CeTarget<EPS...>;
+  static_assert(SMOOTH == TG::SMOOTH && !TG::DROP, "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
+  const TG tg(NC, eps...);
   float loss = 0.f, corr = 0.f, bad = 0.f;
   float cs[LD];   // fp32 column sums of dlogits (dbias: the last layer's bias gradient partial)
 #pragma unroll
@@ -652,30 +619,23 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
     }
     const float inv = 1.f / se;
     const int lab = labels ? labels[row] : -1;
+    typename TG::Row tr = tg.row(lab, row);
     if (labels) {
       float ll = 0.f;
 #pragma unroll
       for (int c = 0; c < LD; ++c) ll = (c == lab) ? l[c] : ll;
-      float lo;
-      if constexpr (MIX) {
-        const int lab2 = mix_labels2(eps...)[row];
-        const float lm = mix_lam(eps...)[row];
-        float lb = 0.f, sd = 0.f;
+      if constexpr (TG::NEEDS_DB) {
+        float lb = 0.f;
 #pragma unroll
-        for (int c = 0; c < LD; ++c) lb = (c == lab2) ? l[c] : lb;
-#pragma unroll
-        for (int c = 0; c < LD; ++c)
-          if (c < NC) sd += l[c] - mx;
-        lo = mix_ce(sm_on, sm_off, mix_logit(lm, ll - mx, lb - mx), sd, __logf(se));
-      } else if constexpr (SMOOTH) {
-        float sd = 0.f;
-#pragma unroll
-        for (int c = 0; c < LD; ++c)
-          if (c < NC) sd += l[c] - mx;
-        lo = fmaf(-sm_off, sd, fmaf(-sm_on, ll - mx, __logf(se)));
-      } else {
-        lo = -(ll - mx - __logf(se));
+        for (int c = 0; c < LD; ++c) lb = (c == tr.yb) ? l[c] : lb;
+        tr.db = lb - mx;
       }
+      if constexpr (TG::NEEDS_SD) {
+#pragma unroll
+        for (int c = 0; c < LD; ++c)
+          if (c < NC) tr.sd += l[c] - mx;
+      }
+      const float lo = tg.loss(tr, ll - mx, __logf(se));
       loss += lo;
       corr += (ll >= mx) ? 1.f : 0.f;
       if (!isfinite(lo)) bad = 1.f;
@@ -687,19 +647,8 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_k(const float* __restrict
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
           const int c0 = 8 * v + 2 * h;
-          float g0, g1;
-          if constexpr (MIX) {
-            const int lab2 = mix_labels2(eps...)[row];   // (the loads of the loss above: merged by the compiler)
-            const float lm = mix_lam(eps...)[row], om = mix_om(lm);
-            g0 = c0 < NC ? (e[c0] * inv - mix_target(c0, lab, lab2, lm, om, sm_on, sm_off)) * scale : 0.f;
-            g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - mix_target(c0 + 1, lab, lab2, lm, om, sm_on, sm_off)) * scale : 0.f;
-          } else if constexpr (SMOOTH) {
-            g0 = c0 < NC ? (e[c0] * inv - (c0 == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
-            g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - (c0 + 1 == lab ? sm_on + sm_off : sm_off)) * scale : 0.f;
-          } else {
-            g0 = c0 < NC ? (e[c0] * inv - (c0 == lab ? 1.f : 0.f)) * scale : 0.f;
-            g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - (c0 + 1 == lab ? 1.f : 0.f)) * scale : 0.f;
-          }
+          const float g0 = c0 < NC ? (e[c0] * inv - tg.q(tr, c0)) * scale : 0.f;
+          const float g1 = c0 + 1 < NC ? (e[c0 + 1] * inv - tg.q(tr, c0 + 1)) * scale : 0.f;
           o[h] = pack2(g0, g1);
           cs[c0] += g0;
           cs[c0 + 1] += g1;

@@ -166,45 +166,6 @@ DEV void dx_tiles(int v0, const bf16_t* i3, const uint32_t (&d3p)[T1][8], bf16_t
   }
 }
 
-// The smoothed loss of a row whose classes (i&3) + 8(i>>2) + 4h live in lanes r and r + 32
-// (ce_stats.h): the masked class sum of l_c - mx, joined across the two half-rows as se and ll are.
-// Both lanes of a row must call it.
-DEV float smooth_loss(const float (&lg)[8], float mx, float se, float ll, int h, int nc, float eps) {
-  const float off = eps / (float)nc, on = 1.f - eps;
-  float sd = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if ((i & 3) + 8 * (i >> 2) + 4 * h < nc) sd += lg[i] - mx;
-  sd += __shfl_xor(sd, 32, 64);
-  return fmaf(-off, sd, fmaf(-on, ll - mx, __logf(se)));
-}
-
-// The two-label loss of such a row (MIX, ce_stats.h): smooth_loss with lam (l_ya - mx) + om (l_yb - mx)
-// in place of l_y - mx; lb is l_yb, found and joined as ll is.  Both lanes of a row must call it.
-DEV float mix_loss(const float (&lg)[8], float mx, float se, float ll, float lb, float lam, int h, int nc, float eps) {
-  const float off = eps / (float)nc, on = 1.f - eps;
-  float sd = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if ((i & 3) + 8 * (i >> 2) + 4 * h < nc) sd += lg[i] - mx;
-  sd += __shfl_xor(sd, 32, 64);
-  return mix_ce(on, off, mix_logit(lam, ll - mx, lb - mx), sd, __logf(se));
-}
-
-// The trailing argument pack of mlp_head_k: eps (SMOOTH) first, then labels2 and lam (MIX, which
-// always comes with eps), then the dropout arguments.  DROP is
-// read off the pack's types instead of being one more template argument, so the plain and the
-// smoothed instantiation keep the names (and the code objects) they had before dropout existed.
-template <typename... A>
-constexpr bool pack_has_drop = (std::is_same_v<A, HeadDrop> || ...);
-DEV float pack_eps(float e) { return e; }
-DEV float pack_eps(float e, const HeadDrop&) { return e; }
-DEV const HeadDrop& pack_drop(const HeadDrop& d) { return d; }
-DEV const HeadDrop& pack_drop(float, const HeadDrop& d) { return d; }
-DEV float pack_eps(float e, const int32_t*, const float*) { return e; }
-DEV float pack_eps(float e, const int32_t*, const float*, const HeadDrop&) { return e; }
-DEV const HeadDrop& pack_drop(float, const int32_t*, const float*, const HeadDrop& d) { return d; }
-
 // The draws of features 8g + 4h .. + 3 (registers 4q .. 4q + 3 of a tile, draw group g = 4 tile + q)
 // of batch row m: words 2h and 2h + 1 of group g's Philox call.  The two half-row lanes need every
 // group; lane half h makes the call of group (g & ~1) + h alone and the two trade the words the other
@@ -234,9 +195,10 @@ DEV void drop_pack(const DropKey& k, float inv_keep, uint32_t m, uint32_t g, int
 // load / compute / store phases in lockstep); TPW = 2 with 4 waves (the next tile's X
 // loads under the current tile's backward chain) measured slower (0.540 vs 0.53 ms/step,
 // profiles/r3/lenet/knobs/).
-// SMOOTH: label smoothing (ce_stats.h), eps as the first member of the trailing argument pack.
-// MIX (labels2 and lam behind eps; gradient form only): two labels and a weight per row (ce_stats.h).
-// l_yb is found as l_ya is, one more select chain and one more __shfl_xor; 8 more bytes read per row.
+// The trailing argument pack [eps] [labels2, lam] [HeadDrop] is read through its CeTarget (ce_stats.h),
+// so the plain and the smoothed instantiation keep the names (and the code objects) they had before
+// the later members existed.  SMOOTH: label smoothing, eps opens the pack.  Two labels and a weight per
+// row (labels2 and lam behind eps; gradient form only): 8 more bytes read per row.
 // DROP (a HeadDrop closes the pack; gradient form only): dropout on h3 and h4 (dropout_rng.h).  The
 // masks are drawn where the activations are packed; h3 / h4 are stored dropped and scaled, so the
 // weight and bias gradients need nothing; the backward reads the bit off the packed activation
@@ -253,11 +215,11 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
                                                   bf16_t* __restrict__ dx, float* __restrict__ stats,
                                                   float* __restrict__ work, int defer_stats,
                                                   float* __restrict__ dbias, EPS... eps) {
-  constexpr bool DROP = pack_has_drop<EPS...>, MIX = pack_has_mix<EPS...>;
-  static_assert(sizeof...(EPS) == (SMOOTH ? 1 : 0) + (MIX ? 2 : 0) + (DROP ? 1 : 0),
-                "the pack is [eps] [labels2, lam] [HeadDrop]");
-  static_assert(GRADS || !DROP, "dropout is a training quantity: the gradient form only");
-  static_assert(!MIX || (SMOOTH && GRADS), "the mixed form takes eps and is the gradient form only");
+  using TG = CeTarget<EPS...>;
+  constexpr bool DROP = TG::DROP;
+  static_assert(SMOOTH == TG::SMOOTH, "SMOOTH says whether eps opens the pack");
+  static_assert(GRADS || !(DROP || TG::MIX), "dropout and two labels are training quantities: the gradient form only");
+  const TG tg(nc, eps...);
   __shared__ __attribute__((aligned(16))) bf16_t i3[R3 * S3];
   __shared__ __attribute__((aligned(16))) bf16_t i4[R4 * S4];
   __shared__ __attribute__((aligned(16))) bf16_t i5[R5 * S5];
@@ -346,7 +308,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
         const int n = 32 * t + 8 * q + 4 * h;
         const f32x4 bb = *(const f32x4*)(bias3 + n);
         if constexpr (DROP) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
-          const HeadDrop& dr = pack_drop(eps...);
+          const HeadDrop& dr = *tg.drop;
           const float v[4] = {fmaxf(a1[t][4 * q] + bb[0], 0.f), fmaxf(a1[t][4 * q + 1] + bb[1], 0.f),
                               fmaxf(a1[t][4 * q + 2] + bb[2], 0.f), fmaxf(a1[t][4 * q + 3] + bb[3], 0.f)};
           drop_pack(drop_key(dr.step, dr.seed, dr.layer3, dr.thr), dr.inv_keep, (uint32_t)m, 4 * t + q, h, v,
@@ -381,7 +343,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
         const int n = 32 * u + 8 * q + 4 * h;
         const f32x4 bb = *(const f32x4*)(bias4 + n);
         if constexpr (DROP) {
-          const HeadDrop& dr = pack_drop(eps...);
+          const HeadDrop& dr = *tg.drop;
           const float v[4] = {fmaxf(a2[u][4 * q] + bb[0], 0.f), fmaxf(a2[u][4 * q + 1] + bb[1], 0.f),
                               fmaxf(a2[u][4 * q + 2] + bb[2], 0.f), fmaxf(a2[u][4 * q + 3] + bb[3], 0.f)};
           drop_pack(drop_key(dr.step, dr.seed, dr.layer4, dr.thr), dr.inv_keep, (uint32_t)m, 4 * u + q, h, v,
@@ -413,78 +375,8 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
       for (int e = 0; e < 4; ++e) lg[4 * q + e] = a3[4 * q + e] + bb[e];
       if (valid) *(f32x4*)(logits + (int64_t)m * LD3 + 8 * q + 4 * h) = f32x4{lg[4 * q], lg[4 * q + 1], lg[4 * q + 2], lg[4 * q + 3]};
     }
-    // ---------------- softmax cross-entropy (a row's classes live in lanes r and r + 32)
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if ((i & 3) + 8 * (i >> 2) + 4 * h < nc) mx = fmaxf(mx, lg[i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float e[8], se = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      e[i] = ((i & 3) + 8 * (i >> 2) + 4 * h < nc) ? __expf(lg[i] - mx) : 0.f;
-      se += e[i];
-    }
-    se += __shfl_xor(se, 32, 64);
-    if (!valid) lab = -1;
-    float ll = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ll = ((i & 3) + 8 * (i >> 2) + 4 * h == lab) ? lg[i] : ll;
-    ll += __shfl_xor(ll, 32, 64);
-    if constexpr (MIX) {
-      const int lab2 = mix_row_label(min(m, nb - 1), eps...);
-      const float lm = mix_row_lam(min(m, nb - 1), eps...);
-      float lb = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) lb = ((i & 3) + 8 * (i >> 2) + 4 * h == lab2) ? lg[i] : lb;
-      lb += __shfl_xor(lb, 32, 64);
-      const float lo = mix_loss(lg, mx, se, ll, lb, lm, h, nc, mix_eps(eps...));   // by both half-rows
-      if (valid && h == 0) {
-        loss += lo;
-        corr += (ll >= mx) ? 1.f : 0.f;
-        bad = isfinite(lo) ? bad : 1.f;
-      }
-    } else if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
-      const float lo = smooth_loss(lg, mx, se, ll, h, nc, pack_eps(eps...));   // by both half-rows
-      if (valid && h == 0) {
-        loss += lo;
-        corr += (ll >= mx) ? 1.f : 0.f;
-        bad = isfinite(lo) ? bad : 1.f;
-      }
-    } else if (valid && h == 0) {
-      const float lo = -(ll - mx - __logf(se));
-      loss += lo;
-      corr += (ll >= mx) ? 1.f : 0.f;
-      bad = isfinite(lo) ? bad : 1.f;
-    }
-    if constexpr (GRADS) {
-      const float inv = 1.f / se;
-      uint32_t dlp[4];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        float g2[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int i = 2 * w + k, cls = (i & 3) + 8 * (i >> 2) + 4 * h;
-          if constexpr (MIX) {      // q_c = (1 - eps) (lam [c == ya] + om [c == yb]) + eps / nc
-            const float off = mix_eps(eps...) / (float)nc, on = 1.f - mix_eps(eps...);
-            const int lab2 = mix_row_label(min(m, nb - 1), eps...);   // (the loads of the loss above: merged by the compiler)
-            const float lm = mix_row_lam(min(m, nb - 1), eps...);
-            g2[k] = cls < nc ? (e[i] * inv - mix_target(cls, lab, lab2, lm, mix_om(lm), on, off)) * scale : 0.f;
-          } else if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
-            const float off = pack_eps(eps...) / (float)nc, on = 1.f - pack_eps(eps...);
-            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? on + off : off)) * scale : 0.f;
-          } else {
-            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? 1.f : 0.f)) * scale : 0.f;
-          }
-          cs[i] += valid ? g2[k] : 0.f;
-        }
-        dlp[w] = pack2(g2[0], g2[1]);
-      }
-      if (valid)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) *(u32x2*)(dl + (int64_t)m * LD3 + 8 * q + 4 * h) = u32x2{dlp[2 * q], dlp[2 * q + 1]};
-
+    // ---------------- softmax cross-entropy; with GRADS: dlogits, and on inside the block this opens
+#include "head_ce_body.h"
       // transposed-read coordinates: group g = lane>>4 supplies rows 4h+q4 (+8), columns 16(g&1)+4p4
       const int q4 = (lane >> 2) & 3, c16 = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
 
@@ -500,7 +392,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
 #pragma unroll
         for (int w = 0; w < 8; ++w) {
           if constexpr (DROP) {   // h4' > 0: kept and past the ReLU
-            const float ik = pack_drop(eps...).inv_keep;
+            const float ik = tg.drop->inv_keep;
             d4p[u][w] = pack2(pos_lo(h4p[u][w]) ? acc[2 * w] * ik : 0.f, pos_hi(h4p[u][w]) ? acc[2 * w + 1] * ik : 0.f);
             continue;
           }
@@ -534,7 +426,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
 #pragma unroll
         for (int w = 0; w < 8; ++w) {
           if constexpr (DROP) {
-            const float ik = pack_drop(eps...).inv_keep;
+            const float ik = tg.drop->inv_keep;
             d3p[t][w] = pack2(pos_lo(h3p[t][w]) ? d3[t][2 * w] * ik : 0.f, pos_hi(h3p[t][w]) ? d3[t][2 * w + 1] * ik : 0.f);
             continue;
           }
@@ -603,9 +495,10 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
                                                      bf16_t* __restrict__ dx, float* __restrict__ stats,
                                                      float* __restrict__ work, int defer_stats,
                                                      float* __restrict__ dbias, EPS... eps) {
-  constexpr bool MIX = pack_has_mix<EPS...>;
-  static_assert(sizeof...(EPS) == (MIX ? 3 : SMOOTH ? 1 : 0) && (!MIX || (SMOOTH && GRADS)),
-                "the smoothed instantiation takes eps, the mixed one eps, labels2 and lam");
+  using TG = CeTarget<EPS...>;
+  static_assert(SMOOTH == TG::SMOOTH && !TG::DROP && (GRADS || !TG::MIX),
+                "the smoothed instantiation takes eps, the mixed one (gradient form only) eps, labels2 and lam");
+  const TG tg(nc, eps...);
   __shared__ __attribute__((aligned(16))) bf16_t i5[16 * TD0];
   __shared__ __attribute__((aligned(16))) float bias5[LD3];
   __shared__ __attribute__((aligned(16))) bf16_t stage[TNW * STG];
@@ -655,76 +548,8 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
       for (int e = 0; e < 4; ++e) lg[4 * q + e] = a3[4 * q + e] + bb[e];
       if (valid) *(f32x4*)(logits + (int64_t)m * LD3 + 8 * q + 4 * h) = f32x4{lg[4 * q], lg[4 * q + 1], lg[4 * q + 2], lg[4 * q + 3]};
     }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if ((i & 3) + 8 * (i >> 2) + 4 * h < nc) mx = fmaxf(mx, lg[i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float e[8], se = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      e[i] = ((i & 3) + 8 * (i >> 2) + 4 * h < nc) ? __expf(lg[i] - mx) : 0.f;
-      se += e[i];
-    }
-    se += __shfl_xor(se, 32, 64);
-    if (!valid) lab = -1;
-    float ll = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ll = ((i & 3) + 8 * (i >> 2) + 4 * h == lab) ? lg[i] : ll;
-    ll += __shfl_xor(ll, 32, 64);
-    if constexpr (MIX) {
-      const int lab2 = mix_row_label(min(m, nb - 1), eps...);
-      const float lm = mix_row_lam(min(m, nb - 1), eps...);
-      float lb = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) lb = ((i & 3) + 8 * (i >> 2) + 4 * h == lab2) ? lg[i] : lb;
-      lb += __shfl_xor(lb, 32, 64);
-      const float lo = mix_loss(lg, mx, se, ll, lb, lm, h, nc, mix_eps(eps...));   // by both half-rows
-      if (valid && h == 0) {
-        loss += lo;
-        corr += (ll >= mx) ? 1.f : 0.f;
-        bad = isfinite(lo) ? bad : 1.f;
-      }
-    } else if constexpr (SMOOTH) {   // (a discarded branch is not instantiated: the plain kernel's code stays as it was)
-      const float lo = smooth_loss(lg, mx, se, ll, h, nc, smooth_eps(eps...));   // by both half-rows
-      if (valid && h == 0) {
-        loss += lo;
-        corr += (ll >= mx) ? 1.f : 0.f;
-        bad = isfinite(lo) ? bad : 1.f;
-      }
-    } else if (valid && h == 0) {
-      const float lo = -(ll - mx - __logf(se));
-      loss += lo;
-      corr += (ll >= mx) ? 1.f : 0.f;
-      bad = isfinite(lo) ? bad : 1.f;
-    }
-    if constexpr (GRADS) {
-      const float inv = 1.f / se;
-      uint32_t dlp[4];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        float g2[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int i = 2 * w + k, cls = (i & 3) + 8 * (i >> 2) + 4 * h;
-          if constexpr (MIX) {      // q_c = (1 - eps) (lam [c == ya] + om [c == yb]) + eps / nc
-            const float off = mix_eps(eps...) / (float)nc, on = 1.f - mix_eps(eps...);
-            const int lab2 = mix_row_label(min(m, nb - 1), eps...);   // (the loads of the loss above: merged by the compiler)
-            const float lm = mix_row_lam(min(m, nb - 1), eps...);
-            g2[k] = cls < nc ? (e[i] * inv - mix_target(cls, lab, lab2, lm, mix_om(lm), on, off)) * scale : 0.f;
-          } else if constexpr (SMOOTH) {   // q_c = (1 - eps) [c == y] + eps / nc in place of the 0 / 1
-            const float off = smooth_eps(eps...) / (float)nc, on = 1.f - smooth_eps(eps...);
-            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? on + off : off)) * scale : 0.f;
-          } else {
-            g2[k] = cls < nc ? (e[i] * inv - (cls == lab ? 1.f : 0.f)) * scale : 0.f;
-          }
-          cs[i] += valid ? g2[k] : 0.f;
-        }
-        dlp[w] = pack2(g2[0], g2[1]);
-      }
-      if (valid)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) *(u32x2*)(dl + (int64_t)m * LD3 + 8 * q + 4 * h) = u32x2{dlp[2 * q], dlp[2 * q + 1]};
+    // with GRADS: dlogits, and on inside the block this opens
+#include "head_ce_body.h"
       // dh4^T[192 x 32] = W5 . dlogits^T, masked by h4 > 0: register k of tile u = feature
       // 32 u + 8 (k >> 2) + 4 h + (k & 3) = chunk 2 u + (k >> 3), word 2 ((k >> 2) & 1) + ((k & 3) >> 1)
       const int q4 = (lane >> 2) & 3, c16 = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
@@ -768,102 +593,74 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
   if (stats) ce_block_stats<TNW>(loss, corr, bad, stats, work, defer_stats != 0);
 }
 
+
+// Launches.  The instantiations of each label target are a translation unit of their own
+// (mlp_head_smooth.hip, mlp_head_drop.hip, mlp_head_mix.hip, which include this text).  In one module
+// with the smoothed ones the plain mlp_head_k<true> came out of the compiler with other address
+// arithmetic and registers (4306 instead of 4290 instructions); apart, this file's code object is what
+// it was before they existed.
+template <typename K, typename... E>
+hipError_t launch_head(K kern, const HeadArgs& a, hipStream_t st, E... extra) {
+  hipLaunchKernelGGL(kern, dim3(mlp_head_blocks(a.nb)), dim3(NTH), 0, st, a.x, a.w3t, a.b3, a.n1, a.w4t, a.b4, a.n2,
+                     a.w5t, a.b5, a.nc, a.labels, a.nb, a.scale, a.h3, a.h4, a.logits, a.dl, a.dh4, a.dh3, a.dx,
+                     a.stats, a.work, a.defer_stats, a.dbias, extra...);
+  return hipGetLastError();
+}
+// ce_tail_k<nw, GRADS, SMOOTH, E...> at the batch's wave count
+template <bool GRADS, bool SMOOTH, typename... E>
+hipError_t launch_tail(const TailArgs& a, hipStream_t st, E... extra) {
+  const int nw = ce_tail_nw(a.nb);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(ce_tail_blocks(a.nb)), dim3(64 * nw), 0, st, a.x, a.w5t, a.b5, a.nc, a.labels, a.nb,
+                       a.scale, a.logits, a.dl, a.dx, a.stats, a.work, a.defer_stats, a.dbias, extra...);
+  };
+  if (nw == 1) go(ce_tail_k<1, GRADS, SMOOTH, E...>);
+  else if (nw == 2) go(ce_tail_k<2, GRADS, SMOOTH, E...>);
+  else go(ce_tail_k<4, GRADS, SMOOTH, E...>);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 #ifdef MNISTX_HEAD_SMOOTH_TU
-// mlp_head_smooth.hip: the smoothed instantiations alone, as a translation unit of their own.  In
-// one module with them the plain mlp_head_k<true> came out of the compiler with other address
-// arithmetic and registers (4306 instead of 4290 instructions); apart, this file's code object
-// is what it was before the smoothed kernels existed.
-hipError_t ce_tail_smooth(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
-                          float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work,
-                          hipStream_t st, int defer_stats, float* dbias, float label_smoothing) {
-  if (nb <= 0) return hipSuccess;
-  if (!dl) return hipErrorInvalidValue;   // a training quantity: the gradient form only
-  const dim3 grid(ce_tail_blocks(nb));
-  const int nw = ce_tail_nw(nb);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(64 * nw), 0, st, x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats,
-                       work, defer_stats, dbias, label_smoothing);
-  };
-  if (nw == 1) go(ce_tail_k<1, true, true, float>);
-  else if (nw == 2) go(ce_tail_k<2, true, true, float>);
-  else go(ce_tail_k<4, true, true, float>);
-  return hipGetLastError();
+hipError_t ce_tail_smooth(const TailArgs& a, hipStream_t st, float label_smoothing) {
+  if (a.nb <= 0) return hipSuccess;
+  if (!a.dl) return hipErrorInvalidValue;   // a training quantity: the gradient form only
+  return launch_tail<true, true>(a, st, label_smoothing);
 }
 
-hipError_t mlp_head_smooth(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
-                           const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
-                           int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
-                           bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
-                           float* dbias, float label_smoothing) {
-  if (nb <= 0) return hipSuccess;
-  if (!dl) return hipErrorInvalidValue;
-  const dim3 grid((nb + ROWS - 1) / ROWS);
-  hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float>), grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4, n2,
-                     w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work, defer_stats, dbias,
-                     label_smoothing);
-  return hipGetLastError();
+hipError_t mlp_head_smooth(const HeadArgs& a, hipStream_t st, float label_smoothing) {
+  if (a.nb <= 0) return hipSuccess;
+  if (!a.dl) return hipErrorInvalidValue;
+  return launch_head(mlp_head_k<true, NWAVE, 1, true, float>, a, st, label_smoothing);
 }
 #elif defined(MNISTX_HEAD_DROP_TU)
-// mlp_head_drop.hip: the dropped instantiations (with and without label smoothing), a translation
-// unit of their own for the same reason.  GRADS = false has no dropped form.
-hipError_t mlp_head_drop(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
-                         const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
-                         int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
-                         bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
-                         float* dbias, float label_smoothing, const HeadDrop& drop) {
-  if (nb <= 0) return hipSuccess;
-  if (!dl || !drop.step) return hipErrorInvalidValue;
-  const dim3 grid((nb + ROWS - 1) / ROWS);
+// GRADS = false has no dropped form
+hipError_t mlp_head_drop(const HeadArgs& a, hipStream_t st, float label_smoothing, const HeadDrop& drop) {
+  if (a.nb <= 0) return hipSuccess;
+  if (!a.dl || !drop.step) return hipErrorInvalidValue;
   if (label_smoothing != 0.f)
-    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float, HeadDrop>), grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t,
-                       b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work,
-                       defer_stats, dbias, label_smoothing, drop);
-  else
-    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, false, HeadDrop>), grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4,
-                       n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work, defer_stats,
-                       dbias, drop);
-  return hipGetLastError();
+    return launch_head(mlp_head_k<true, NWAVE, 1, true, float, HeadDrop>, a, st, label_smoothing, drop);
+  return launch_head(mlp_head_k<true, NWAVE, 1, false, HeadDrop>, a, st, drop);
 }
 #elif defined(MNISTX_HEAD_MIX_TU)
-// mlp_head_mix.hip: the two-label instantiations (mixup / CutMix; eps always in the pack, 0 allowed)
-// of both fused heads, with dropout and without, a translation unit of their own for the same reason.
-hipError_t ce_tail_mix(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
-                       float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                       int defer_stats, float* dbias, float label_smoothing, const int32_t* labels2, const float* lam) {
-  if (nb <= 0) return hipSuccess;
-  if (!dl || !labels2 || !lam) return hipErrorInvalidValue;   // a training quantity: the gradient form only
-  const dim3 grid(ce_tail_blocks(nb));
-  const int nw = ce_tail_nw(nb);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(64 * nw), 0, st, x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats,
-                       work, defer_stats, dbias, label_smoothing, labels2, lam);
-  };
-  if (nw == 1) go(ce_tail_k<1, true, true, float, const int32_t*, const float*>);
-  else if (nw == 2) go(ce_tail_k<2, true, true, float, const int32_t*, const float*>);
-  else go(ce_tail_k<4, true, true, float, const int32_t*, const float*>);
-  return hipGetLastError();
+// eps is always in the pack, 0 allowed
+hipError_t ce_tail_mix(const TailArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2,
+                       const float* lam) {
+  if (a.nb <= 0) return hipSuccess;
+  if (!a.dl || !labels2 || !lam) return hipErrorInvalidValue;   // a training quantity: the gradient form only
+  return launch_tail<true, true>(a, st, label_smoothing, labels2, lam);
 }
 
-hipError_t mlp_head_mix(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t,
-                        const float* b4, int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels,
-                        int nb, float scale, bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4,
-                        bf16_t* dh3, bf16_t* dx, float* stats, float* work, hipStream_t st, int defer_stats,
-                        float* dbias, float label_smoothing, const int32_t* labels2, const float* lam,
-                        const HeadDrop* drop) {
-  if (nb <= 0) return hipSuccess;
-  if (!dl || !labels2 || !lam || (drop && !drop->step)) return hipErrorInvalidValue;
-  const dim3 grid((nb + ROWS - 1) / ROWS);
+hipError_t mlp_head_mix(const HeadArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2,
+                        const float* lam, const HeadDrop* drop) {
+  if (a.nb <= 0) return hipSuccess;
+  if (!a.dl || !labels2 || !lam || (drop && !drop->step)) return hipErrorInvalidValue;
   if (drop)
-    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float, const int32_t*, const float*, HeadDrop>), grid,
-                       dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits,
-                       dl, dh4, dh3, dx, stats, work, defer_stats, dbias, label_smoothing, labels2, lam, *drop);
-  else
-    hipLaunchKernelGGL((mlp_head_k<true, NWAVE, 1, true, float, const int32_t*, const float*>), grid, dim3(NTH), 0, st,
-                       x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx,
-                       stats, work, defer_stats, dbias, label_smoothing, labels2, lam);
-  return hipGetLastError();
+    return launch_head(mlp_head_k<true, NWAVE, 1, true, float, const int32_t*, const float*, HeadDrop>, a, st,
+                       label_smoothing, labels2, lam, *drop);
+  return launch_head(mlp_head_k<true, NWAVE, 1, true, float, const int32_t*, const float*>, a, st, label_smoothing,
+                     labels2, lam);
 }
 #else
 // waves per block (32 rows each): 2, or more when the block count would exceed the CE partial
@@ -882,66 +679,36 @@ int ce_tail_nw(int nb) {
 int ce_tail_blocks(int nb) { const int r = 32 * ce_tail_nw(nb); return (nb + r - 1) / r; }
 bool ce_tail_supported(int d0, int nc, int B) { return d0 == TD0 && nc > 0 && nc <= LD3 && B > 0 && ce_tail_blocks(B) <= CE_MAXB; }
 
-hipError_t ce_tail(const bf16_t* x, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb,
-                   float scale, float* logits, bf16_t* dl, bf16_t* dx, float* stats, float* work, hipStream_t st,
-                   int defer_stats, float* dbias, float label_smoothing, const int32_t* labels2, const float* lam) {
+// the eval forms (dl == nullptr) write no bias gradient
+hipError_t ce_tail(const TailArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2, const float* lam) {
   if ((labels2 != nullptr) != (lam != nullptr)) return hipErrorInvalidValue;
-  if (labels2)
-    return ce_tail_mix(x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats, work, st, defer_stats, dbias,
-                       label_smoothing, labels2, lam);
-  if (label_smoothing != 0.f)
-    return ce_tail_smooth(x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats, work, st, defer_stats, dbias,
-                          label_smoothing);
-  if (nb <= 0) return hipSuccess;
-  const dim3 grid(ce_tail_blocks(nb));
-  const int nw = ce_tail_nw(nb);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(64 * nw), 0, st, x, w5t, b5, nc, labels, nb, scale, logits, dl, dx, stats,
-                       work, defer_stats, dl ? dbias : nullptr);
-  };
-  if (dl) {
-    if (nw == 1) go(ce_tail_k<1, true>);
-    else if (nw == 2) go(ce_tail_k<2, true>);
-    else go(ce_tail_k<4, true>);
-  } else {
-    if (nw == 1) go(ce_tail_k<1, false>);
-    else if (nw == 2) go(ce_tail_k<2, false>);
-    else go(ce_tail_k<4, false>);
-  }
-  return hipGetLastError();
+  if (labels2) return ce_tail_mix(a, st, label_smoothing, labels2, lam);
+  if (label_smoothing != 0.f) return ce_tail_smooth(a, st, label_smoothing);
+  if (a.nb <= 0) return hipSuccess;
+  if (a.dl) return launch_tail<true, false>(a, st);
+  TailArgs e = a;
+  e.dbias = nullptr;
+  return launch_tail<false, false>(e, st);
 }
 
-int mlp_head_blocks(int nb) { return (nb + ROWS - 1) / ROWS; }
+int mlp_head_blocks(int nb) { return (nb + ROWS - 1) / ROWS; }   // ROWS rows per block
 
 bool mlp_head_supported(int d0, int ld1, int ld2, int ld3, int n1, int n2, int nc, int B) {
   return d0 == D0 && ld1 == LD1 && ld2 == LD2 && ld3 == LD3 && n1 <= LD1 && n2 <= LD2 && nc <= LD3 && nc > 0 &&
          B > 0 && (B + ROWS - 1) / ROWS <= CE_MAXB;
 }
 
-hipError_t mlp_head(const bf16_t* x, const bf16_t* w3t, const float* b3, int n1, const bf16_t* w4t, const float* b4,
-                    int n2, const bf16_t* w5t, const float* b5, int nc, const int32_t* labels, int nb, float scale,
-                    bf16_t* h3, bf16_t* h4, float* logits, bf16_t* dl, bf16_t* dh4, bf16_t* dh3, bf16_t* dx,
-                    float* stats, float* work, hipStream_t st, int defer_stats, float* dbias, float label_smoothing,
-                    const HeadDrop* drop, const int32_t* labels2, const float* lam) {
+hipError_t mlp_head(const HeadArgs& a, hipStream_t st, float label_smoothing, const HeadDrop* drop,
+                    const int32_t* labels2, const float* lam) {
   if ((labels2 != nullptr) != (lam != nullptr)) return hipErrorInvalidValue;
-  if (labels2)
-    return mlp_head_mix(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx,
-                        stats, work, st, defer_stats, dbias, label_smoothing, labels2, lam, drop);
-  if (drop)
-    return mlp_head_drop(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3, dx,
-                         stats, work, st, defer_stats, dbias, label_smoothing, *drop);
-  if (label_smoothing != 0.f)
-    return mlp_head_smooth(x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb, scale, h3, h4, logits, dl, dh4, dh3,
-                           dx, stats, work, st, defer_stats, dbias, label_smoothing);
-  if (nb <= 0) return hipSuccess;
-  const dim3 grid((nb + ROWS - 1) / ROWS);   // ROWS rows per block
-  if (dl)
-    hipLaunchKernelGGL(mlp_head_k<true>, grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb,
-                       scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work, defer_stats, dbias);
-  else
-    hipLaunchKernelGGL(mlp_head_k<false>, grid, dim3(NTH), 0, st, x, w3t, b3, n1, w4t, b4, n2, w5t, b5, nc, labels, nb,
-                       scale, h3, h4, logits, dl, dh4, dh3, dx, stats, work, defer_stats, nullptr);
-  return hipGetLastError();
+  if (labels2) return mlp_head_mix(a, st, label_smoothing, labels2, lam, drop);
+  if (drop) return mlp_head_drop(a, st, label_smoothing, *drop);
+  if (label_smoothing != 0.f) return mlp_head_smooth(a, st, label_smoothing);
+  if (a.nb <= 0) return hipSuccess;
+  if (a.dl) return launch_head(mlp_head_k<true>, a, st);
+  HeadArgs e = a;
+  e.dbias = nullptr;
+  return launch_head(mlp_head_k<false>, e, st);
 }
 #endif
 
