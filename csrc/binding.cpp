@@ -552,12 +552,52 @@ MixArgs mix_args(const optional<Tensor>& labels2, const optional<Tensor>& lam, i
   return a;
 }
 
+// teacher_logits / teacher_ld / distill_alpha / distill_temperature of the softmax-CE bindings (knowledge
+// distillation, ce_stats.h DISTILL).  All of it is checked before anything is launched (ValueError):
+// alpha finite in [0, 1]; T finite and > 0 with T * T finite in fp32; the teacher fp32, contiguous, on
+// `like`'s device, teacher_ld >= nc and at least nb * teacher_ld elements; never together with a
+// non-zero label_smoothing, labels2 / lam or dropout.  on == false (no teacher, or alpha == 0): the launch
+// without the keywords.
+struct DistillArgs {
+  bool on = false;
+  mnistx::CeDistill d{};
+};
+DistillArgs distill_args(const optional<Tensor>& teacher, int64_t ld, double alpha, double T, int64_t nb, int64_t nc,
+                         const Tensor& like, float eps, bool mixed, bool dropped, const char* op) {
+  TORCH_CHECK_VALUE(std::isfinite(alpha) && alpha >= 0.0 && alpha <= 1.0, op,
+                    ": distill_alpha must be finite with 0 <= distill_alpha <= 1, got ", alpha);
+  const float Tf = (float)T;
+  TORCH_CHECK_VALUE(std::isfinite(T) && T > 0.0 && Tf > 0.f && std::isfinite(Tf * Tf) && std::isfinite(1.f / Tf), op,
+                    ": distill_temperature must be finite and > 0 with its square finite in fp32, got ", T);
+  DistillArgs a;
+  if (!(teacher.has_value() && teacher->defined())) return a;
+  TORCH_CHECK_VALUE(eps == 0.f, op, ": teacher_logits cannot be combined with label_smoothing (", eps, ")");
+  TORCH_CHECK_VALUE(!mixed, op, ": teacher_logits cannot be combined with labels2 / lam");
+  TORCH_CHECK_VALUE(!dropped, op, ": teacher_logits cannot be combined with dropout");
+  TORCH_CHECK_VALUE(teacher->is_cuda() && teacher->device() == like.device(), op,
+                    ": teacher_logits must be a GPU tensor on the logits' device, got ", teacher->device());
+  TORCH_CHECK_VALUE(teacher->scalar_type() == at::kFloat, op, ": teacher_logits must be float32, got ",
+                    teacher->scalar_type());
+  TORCH_CHECK_VALUE(teacher->is_contiguous(), op, ": teacher_logits must be contiguous");
+  TORCH_CHECK_VALUE(ld >= nc && ld < ((int64_t)1 << 31), op, ": teacher_ld must be >= n_classes (", nc, "), got ", ld);
+  TORCH_CHECK_VALUE(nb >= 0 && teacher->numel() >= nb * ld, op, ": teacher_logits needs ", nb * ld, " elements (",
+                    nb, " rows of teacher_ld ", ld, "), has ", teacher->numel());
+  if (alpha == 0.0) return a;   // the plain launch
+  a.on = true;
+  a.d = mnistx::CeDistill{P<const float>(*teacher), (int)ld, (float)alpha, Tf, 1.f / Tf};
+  return a;
+}
+
 int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t B, int64_t NC, double scale,
                    optional<Tensor> dlogits, int64_t ldd, optional<Tensor> stats, optional<Tensor> probs,
                    optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing,
-                   optional<Tensor> labels2, optional<Tensor> lam) {
+                   optional<Tensor> labels2, optional<Tensor> lam, optional<Tensor> teacher_logits, int64_t teacher_ld,
+                   double distill_alpha, double distill_temperature) {
   const float eps = smoothing_arg(label_smoothing, "softmax_ce");
   const MixArgs mx = mix_args(labels2, lam, B, labels.has_value() && labels->defined() ? &*labels : nullptr, "softmax_ce");
+  const DistillArgs ds = distill_args(teacher_logits, teacher_ld, distill_alpha, distill_temperature, B, NC, logits, eps,
+                                      mx.labels2 != nullptr, false, "softmax_ce");
+  TORCH_CHECK_VALUE(!ds.on || (labels.has_value() && labels->defined()), "softmax_ce: teacher_logits needs labels");
   TORCH_CHECK(ldl >= NC, "ldl < NC");
   check(logits, at::kFloat, B * ldl, "logits");   // whole padded rows (vector loads)
   const int32_t* lab = nullptr;
@@ -599,7 +639,8 @@ int64_t softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t 
   }
   int deferred = 0;
   hip_ok(mnistx::softmax_ce(P<const float>(logits), (int)ldl, lab, (int)B, (int)NC, (float)scale, dl, (int)ldd, st, pr,
-                            wk, cur_stream(), defer_stats ? &deferred : nullptr, db, eps, mx.labels2, mx.lam),
+                            wk, cur_stream(), defer_stats ? &deferred : nullptr, db, eps, mx.labels2, mx.lam,
+                            ds.on ? &ds.d : nullptr),
          "softmax_ce");
   return deferred;   // blocks whose CE partials the caller's finalize_step must combine
 }
@@ -617,9 +658,14 @@ bool ce_tail_supported(int64_t d0, int64_t nc, int64_t B) { return mnistx::ce_ta
 // the reference CNN's softmax_linear + softmax CE (+ data gradient masked by x > 0): mlp_head.hip ce_tail_k
 void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t nb, double scale, Tensor logits,
              optional<Tensor> dl, optional<Tensor> dx, Tensor stats, optional<Tensor> work, bool defer_stats,
-             optional<Tensor> dbias, double label_smoothing, optional<Tensor> labels2, optional<Tensor> lam) {
+             optional<Tensor> dbias, double label_smoothing, optional<Tensor> labels2, optional<Tensor> lam,
+             optional<Tensor> teacher_logits, int64_t teacher_ld, double distill_alpha, double distill_temperature) {
   const float eps = smoothing_arg(label_smoothing, "ce_tail");
   const MixArgs mx = mix_args(labels2, lam, nb, &labels, "ce_tail");
+  const DistillArgs ds = distill_args(teacher_logits, teacher_ld, distill_alpha, distill_temperature, nb, nc, x, eps,
+                                      mx.labels2 != nullptr, false, "ce_tail");
+  TORCH_CHECK_VALUE(!ds.on || (dl.has_value() && dl->defined()),
+                    "ce_tail: teacher_logits is a training quantity and needs dl");
   TORCH_CHECK(mnistx::ce_tail_supported(192, (int)nc, (int)std::max<int64_t>(nb, 1)), "ce_tail: unsupported geometry");
   check(x, at::kBFloat16, nb * 192, "x");
   check(w5t, at::kBFloat16, 16 * 192, "w5t");
@@ -652,7 +698,7 @@ void ce_tail(Tensor x, Tensor w5t, Tensor b5, int64_t nc, Tensor labels, int64_t
   const mnistx::TailArgs a{BF(x), BF(w5t), P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale,
                            P<float>(logits), pdl, pdx, P<float>(stats), has_work ? P<float>(*work) : nullptr,
                            defer_stats ? 1 : 0, db};
-  hip_ok(mnistx::ce_tail(a, cur_stream(), eps, mx.labels2, mx.lam), "ce_tail");
+  hip_ok(mnistx::ce_tail(a, cur_stream(), eps, mx.labels2, mx.lam, ds.on ? &ds.d : nullptr), "ce_tail");
 }
 
 // The dropout arguments of a binding, validated (ValueError): the drop rate p (finite, 0 <= p < 1) as
@@ -682,10 +728,15 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
               optional<Tensor> dl, optional<Tensor> dh4, optional<Tensor> dh3, optional<Tensor> dx, Tensor stats,
               optional<Tensor> work, bool defer_stats, optional<Tensor> dbias, double label_smoothing, double dropout,
               optional<Tensor> drop_step, int64_t drop_seed, int64_t drop_layer3, int64_t drop_layer4,
-              optional<Tensor> labels2, optional<Tensor> lam) {
+              optional<Tensor> labels2, optional<Tensor> lam, optional<Tensor> teacher_logits, int64_t teacher_ld,
+              double distill_alpha, double distill_temperature) {
   const float eps = smoothing_arg(label_smoothing, "mlp_head");
   const MixArgs mx = mix_args(labels2, lam, nb, &labels, "mlp_head");
   const DropArgs da = dropout_rate(dropout, "mlp_head");
+  const DistillArgs ds = distill_args(teacher_logits, teacher_ld, distill_alpha, distill_temperature, nb, nc, x, eps,
+                                      mx.labels2 != nullptr, dropout != 0.0, "mlp_head");
+  TORCH_CHECK_VALUE(!ds.on || (dl.has_value() && dl->defined()),
+                    "mlp_head: teacher_logits is a training quantity and needs dl");
   mnistx::HeadDrop hd{};
   if (dropout != 0.0) {   // 0 launches what is launched without the key
     TORCH_CHECK_VALUE(drop_step.has_value() && drop_step->defined(), "mlp_head: dropout needs drop_step");
@@ -742,7 +793,8 @@ void mlp_head(Tensor x, Tensor w3t, Tensor b3, int64_t n1, Tensor w4t, Tensor b4
                            P<const float>(b5), (int)nc, P<const int32_t>(labels), (int)nb, (float)scale, BFm(h3),
                            BFm(h4), P<float>(logits), pdl, pdh4, pdh3, pdx, P<float>(stats),
                            has_work ? P<float>(*work) : nullptr, (defer_stats && has_work) ? 1 : 0, db};
-  hip_ok(mnistx::mlp_head(a, cur_stream(), eps, hd.step ? &hd : nullptr, mx.labels2, mx.lam), "mlp_head");
+  hip_ok(mnistx::mlp_head(a, cur_stream(), eps, hd.step ? &hd : nullptr, mx.labels2, mx.lam, ds.on ? &ds.d : nullptr),
+         "mlp_head");
 }
 
 // stand-alone dropout (dropout.hip), in place on x [nb, ld] bf16 with n real columns
@@ -1847,8 +1899,12 @@ void f32_lrn_pool_bwd(Tensor x, Tensor dy, Tensor arg, Tensor dx, int64_t Nb, in
 
 void f32_softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t B, int64_t NC, double scale,
                     optional<Tensor> dlogits, int64_t ldd, optional<Tensor> stats, optional<Tensor> probs,
-                    optional<Tensor> work, double label_smoothing) {
+                    optional<Tensor> work, double label_smoothing, optional<Tensor> teacher_logits, int64_t teacher_ld,
+                    double distill_alpha, double distill_temperature) {
   const float eps = smoothing_arg(label_smoothing, "f32_softmax_ce");
+  const DistillArgs ds = distill_args(teacher_logits, teacher_ld, distill_alpha, distill_temperature, B, NC, logits, eps,
+                                      false, false, "f32_softmax_ce");
+  TORCH_CHECK_VALUE(!ds.on || (labels.has_value() && labels->defined()), "f32_softmax_ce: teacher_logits needs labels");
   TORCH_CHECK(ldl >= NC, "ldl < NC");
   check(logits, at::kFloat, span(B, ldl, NC), "logits");
   const int32_t* lab = nullptr;
@@ -1879,7 +1935,7 @@ void f32_softmax_ce(Tensor logits, int64_t ldl, optional<Tensor> labels, int64_t
   }
   TORCH_CHECK(eps == 0.f || lab != nullptr, "f32_softmax_ce: label_smoothing needs labels");
   hip_ok(mnistx::f32_softmax_ce(P<const float>(logits), (int)ldl, lab, (int)B, (int)NC, (float)scale, dl, (int)ldd,
-                                st, pr, wk, cur_stream(), eps),
+                                st, pr, wk, cur_stream(), eps, ds.on ? &ds.d : nullptr),
          "f32_softmax_ce");
 }
 
@@ -1925,7 +1981,8 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("f32_lrn_pool_bwd", &f32_lrn_pool_bwd);
   m.def("f32_softmax_ce", &f32_softmax_ce, py::arg("logits"), py::arg("ldl"), py::arg("labels"), py::arg("B"),
         py::arg("NC"), py::arg("scale"), py::arg("dlogits"), py::arg("ldd"), py::arg("stats"), py::arg("probs"),
-        py::arg("work") = py::none(), py::arg("label_smoothing") = 0.0);
+        py::arg("work") = py::none(), py::arg("label_smoothing") = 0.0, py::arg("teacher_logits") = py::none(), py::arg("teacher_ld") = 0,
+        py::arg("distill_alpha") = 0.0, py::arg("distill_temperature") = 1.0);
   m.def("f32_prep_images", &f32_prep_images);
   // test hook: cap every persistent kernel's grid (0 = off) so small-batch oracle tests run
   // the multi-iteration (several tiles per block) paths the benchmark batches run
@@ -1997,7 +2054,8 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("softmax_ce", &softmax_ce, py::arg("logits"), py::arg("ldl"), py::arg("labels"), py::arg("B"), py::arg("NC"),
         py::arg("scale"), py::arg("dlogits"), py::arg("ldd"), py::arg("stats"), py::arg("probs"),
         py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
-        py::arg("label_smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none());
+        py::arg("label_smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none(), py::arg("teacher_logits") = py::none(), py::arg("teacher_ld") = 0,
+        py::arg("distill_alpha") = 0.0, py::arg("distill_temperature") = 1.0);
   m.def("softmax_ce_dbias_blocks",
         [](int64_t B, int64_t ldl) { return (int64_t)mnistx::softmax_ce_dbias_blocks((int)B, (int)ldl); });
   m.def("splitk_reduce", &splitk_reduce);
@@ -2008,7 +2066,8 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("ce_tail", &ce_tail, py::arg("x"), py::arg("w5t"), py::arg("b5"), py::arg("nc"), py::arg("labels"),
         py::arg("nb"), py::arg("scale"), py::arg("logits"), py::arg("dl") = py::none(), py::arg("dx") = py::none(),
         py::arg("stats"), py::arg("work") = py::none(), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
-        py::arg("label_smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none());
+        py::arg("label_smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none(), py::arg("teacher_logits") = py::none(), py::arg("teacher_ld") = 0,
+        py::arg("distill_alpha") = 0.0, py::arg("distill_temperature") = 1.0);
   m.def("mlp_head", &mlp_head, py::arg("x"), py::arg("w3t"), py::arg("b3"), py::arg("n1"), py::arg("w4t"),
         py::arg("b4"), py::arg("n2"), py::arg("w5t"), py::arg("b5"), py::arg("nc"), py::arg("labels"), py::arg("nb"),
         py::arg("scale"), py::arg("h3"), py::arg("h4"), py::arg("logits"), py::arg("dl") = py::none(),
@@ -2016,7 +2075,8 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("work"), py::arg("defer_stats") = false, py::arg("dbias") = py::none(),
         py::arg("label_smoothing") = 0.0, py::arg("dropout") = 0.0, py::arg("drop_step") = py::none(),
         py::arg("drop_seed") = 0, py::arg("drop_layer3") = 0, py::arg("drop_layer4") = 0,
-        py::arg("labels2") = py::none(), py::arg("lam") = py::none());
+        py::arg("labels2") = py::none(), py::arg("lam") = py::none(), py::arg("teacher_logits") = py::none(), py::arg("teacher_ld") = 0,
+        py::arg("distill_alpha") = 0.0, py::arg("distill_temperature") = 1.0);
   m.def("dropout_fwd", &dropout_fwd, py::arg("x"), py::arg("nb"), py::arg("n"), py::arg("ld"), py::arg("step"),
         py::arg("seed"), py::arg("layer"), py::arg("p"));
   m.def("dropout_bwd", &dropout_bwd, py::arg("dy"), py::arg("nb"), py::arg("n"), py::arg("ld"), py::arg("step"),

@@ -13,8 +13,8 @@
 using mnistx::CE_MAXB;   // max blocks per launch (work holds 4 floats per block + ticket)
 
 // The label target of the softmax-CE kernels, one view of their trailing argument pack.  The pack is
-// [eps] [labels2, lam] [HeadDrop]; what it holds is read off its types, so the plain instantiation has
-// no trailing argument and keeps the arguments and the code it always had.
+// [eps] [labels2, lam] [HeadDrop], or a CeDistill alone; what it holds is read off its types, so the
+// plain instantiation has no trailing argument and keeps the arguments and the code it always had.
 //   SMOOTH (eps): label smoothing.  With on = 1 - eps and off = eps / NC (NC = the real class count):
 //     loss = log(se) - on * (l_y - mx) - off * sum_{c < NC} (l_c - mx)
 //     dl_c = (p_c - on * [c == y] - off) * scale
@@ -28,6 +28,20 @@ using mnistx::CE_MAXB;   // max blocks per launch (work holds 4 floats per block
 //   class no label names makes it -inf, and 0 * inf is NaN.  lam + om is exactly 1 for lam in [0.5, 1],
 //   so ya == yb gives `on` at that class.  The top-1 count stays l_ya >= mx: ya is the dominant label.
 //   DROP (a HeadDrop closes the pack; mlp_head_k alone): dropout on the hidden layers (dropout_rng.h).
+//   DISTILL (a CeDistill, launchers.h, alone in the pack): the dense soft target of a frozen teacher at a
+//   temperature (Hinton-style knowledge distillation).  With t_c the teacher's logits of the row, a = alpha,
+//   iT = 1 / T and d_c = l_c - mx:
+//     u_c = d_c * iT               seT = sum exp(u_c)   pT_c = exp(u_c) / seT
+//     v_c = (t_c - max_c t_c) * iT st  = sum exp(v_c)   q_c  = exp(v_c) / st
+//     soft = sum_c q_c * ((v_c - log st) - (u_c - log seT))          KL(q || pT), formed per class
+//     loss = (1 - a) * hard + a * T^2 * soft,   hard = log(se) - d_y (the plain row loss)
+//     dl_c = ((1 - a) * (p_c - [c == y]) + a * T * (pT_c - q_c)) * scale
+//   The KL is summed per class, never as a difference of two sums: equal student and teacher rows give
+//   soft == 0 and a zero soft gradient without cancellation.  q_c == 0 (underflow) contributes 0 while
+//   the other factor is finite; a non-finite teacher or student logit makes the row's loss non-finite
+//   (the NaN flag).  The kernel loads the teacher's row once (trow) and fills in the Row: soft, and
+//   ps[i] = pT_c - q_c of the classes the thread holds, in the kernel's own class layout; dgrad() joins
+//   the two gradients.
 // A kernel builds one CeTarget from (NC, eps...) and one Row per batch row (the second label and the
 // weight are loaded there, once), fills in what the row's loss reads beside da = l_ya - mx and lse =
 // log(se) -- db = l_yb - mx where the Row has it, the class sum sd likewise -- and asks for the row's
@@ -36,21 +50,31 @@ using mnistx::CE_MAXB;   // max blocks per launch (work holds 4 floats per block
 struct CeRow { int ya; };
 struct CeRowSmooth { int ya; float sd; };
 struct CeRowMix { int ya, yb; float lam, om, db, sd; };
+// DISTILL: soft = KL(q || pT) and ps[i] = pT_c - q_c of the (at most 32) classes a thread holds; the members
+// a kernel does not touch cost nothing (every index is a constant after unrolling).  The generic
+// kernels (a run-time class count, no per-class registers) keep the row's scalars instead -- tm = max_c
+// t_c, ist = 1 / st, iseT = 1 / seT -- and form v_c and u_c again where they need them, as they form
+// l_c - mx again.
+struct CeRowDistill { int ya; float soft, tm, ist, iseT; float ps[32]; };
 
 template <typename... P>
 struct CeTarget {
   static constexpr bool SMOOTH = (std::is_same_v<P, float> || ...);
   static constexpr bool MIX = (std::is_same_v<P, const float*> || ...);
   static constexpr bool DROP = (std::is_same_v<P, mnistx::HeadDrop> || ...);
-  static_assert(sizeof...(P) == (SMOOTH ? 1 : 0) + (MIX ? 2 : 0) + (DROP ? 1 : 0) && (SMOOTH || !MIX),
-                "the pack is [eps] [labels2, lam] [HeadDrop]; labels2 and lam come with eps");
+  static constexpr bool DISTILL = (std::is_same_v<P, mnistx::CeDistill> || ...);
+  static_assert(sizeof...(P) == (SMOOTH ? 1 : 0) + (MIX ? 2 : 0) + (DROP ? 1 : 0) + (DISTILL ? 1 : 0) &&
+                    (SMOOTH || !MIX) && (!DISTILL || sizeof...(P) == 1),
+                "the pack is [eps] [labels2, lam] [HeadDrop], or a CeDistill alone; labels2 and lam come with eps");
   static constexpr bool NEEDS_DB = MIX, NEEDS_SD = SMOOTH;   // the Row has db / sd for the kernel to fill in
-  using Row = std::conditional_t<MIX, CeRowMix, std::conditional_t<SMOOTH, CeRowSmooth, CeRow>>;
+  using Row = std::conditional_t<MIX, CeRowMix,
+                                 std::conditional_t<SMOOTH, CeRowSmooth, std::conditional_t<DISTILL, CeRowDistill, CeRow>>>;
 
   float on = 1.f, off = 0.f;
   const int32_t* labels2 = nullptr;
   const float* lam = nullptr;
   const mnistx::HeadDrop* drop = nullptr;
+  const mnistx::CeDistill* dist = nullptr;
 
   DEV CeTarget(int nc, const P&... p) { (take(nc, p), ...); }
 
@@ -62,6 +86,10 @@ struct CeTarget {
       return Row{ya, labels2[m], lm, lm < 1.f ? 1.f - lm : 0.f, 0.f, 0.f};
     } else if constexpr (SMOOTH) {
       return Row{ya, 0.f};
+    } else if constexpr (DISTILL) {
+      Row r;
+      r.ya = ya;
+      return r;
     } else {
       return Row{ya};
     }
@@ -73,6 +101,8 @@ struct CeTarget {
       return off != 0.f ? fmaf(-off, r.sd, a) : a;
     } else if constexpr (SMOOTH) {
       return fmaf(-off, r.sd, fmaf(-on, da, lse));
+    } else if constexpr (DISTILL) {   // (1 - a) * hard + a * T^2 * soft
+      return fmaf(dist->alpha * dist->T * dist->T, r.soft, (1.f - dist->alpha) * -(da - lse));
     } else {
       return -(da - lse);
     }
@@ -82,6 +112,11 @@ struct CeTarget {
     else if constexpr (SMOOTH) return c == r.ya ? on + off : off;
     else return c == r.ya ? 1.f : 0.f;
   }
+  // DISTILL (q() is the one-hot there): the teacher's logits of row m (the fused heads pass min(m, nb - 1),
+  // as for row()),
+  DEV const float* trow(int64_t m) const { return dist->t + m * dist->ldt; }
+  // and a class's gradient from ph = p_c - [c == y] and ps = pT_c - q_c
+  DEV float dgrad(float ph, float ps) const { return fmaf(dist->alpha * dist->T, ps, (1.f - dist->alpha) * ph); }
 
  private:
   DEV void take(int nc, float eps) {
@@ -91,6 +126,7 @@ struct CeTarget {
   DEV void take(int, const int32_t* l2) { labels2 = l2; }
   DEV void take(int, const float* lm) { lam = lm; }
   DEV void take(int, const mnistx::HeadDrop& d) { drop = &d; }
+  DEV void take(int, const mnistx::CeDistill& d) { dist = &d; }
 };
 
 // Every thread of the block must call this (it synchronises the block).

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void lrn_f32_bwd_k(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------- softmax cross-entropy, fp32 gradient
-// The label target (plain, or SMOOTH: eps) is the trailing pack's CeTarget (ce_stats.h).
+// The label target (plain, SMOOTH: eps, or DISTILL: a CeDistill) is the trailing pack's CeTarget (ce_stats.h).
 template <bool SMOOTH = false, typename... EPS>
 __global__ __launch_bounds__(256) void softmax_ce_f32_k(const float* __restrict__ logits, int ldl,
                                                         const int32_t* __restrict__ labels, int B, int NC,
@@ -436,6 +436,26 @@ __global__ __launch_bounds__(256) void softmax_ce_f32_k(const float* __restrict_
     const float inv = 1.f / se;
     const int lab = labels ? labels[row] : -1;
     typename TG::Row tr = tg.row(lab, row);
+    if constexpr (TG::DISTILL) {   // the scalars of the row's soft part (ce_stats.h)
+      typename TG::Row& sf = tr;
+      const float* tp = tg.trow(row);
+      const float iT = tg.dist->iT;
+      sf.tm = -INFINITY;
+      for (int c = 0; c < NC; ++c) sf.tm = fmaxf(sf.tm, tp[c]);
+      float st = 0.f, seT = 0.f;
+      for (int c = 0; c < NC; ++c) {
+        st += expf((tp[c] - sf.tm) * iT);
+        seT += expf((l[c] - mx) * iT);
+      }
+      sf.ist = 1.f / st;
+      sf.iseT = 1.f / seT;
+      const float lst = logf(st), lseT = logf(seT);
+      sf.soft = 0.f;
+      for (int c = 0; c < NC; ++c) {
+        const float v = (tp[c] - sf.tm) * iT;
+        sf.soft += expf(v) * sf.ist * ((v - lst) - ((l[c] - mx) * iT - lseT));
+      }
+    }
     if (labels) {
       const float ll = l[lab];
       if constexpr (TG::NEEDS_SD)
@@ -446,8 +466,18 @@ __global__ __launch_bounds__(256) void softmax_ce_f32_k(const float* __restrict_
       if (!isfinite(lo)) bad = 1.f;
     }
     if (dl)
-      for (int c = 0; c < ldd; ++c)
+      for (int c = 0; c < ldd; ++c) {
+        if constexpr (TG::DISTILL) {
+          float g = 0.f;
+          if (c < NC) {
+            const float* tp = tg.trow(row);
+            const float ps = expf((l[c] - mx) * tg.dist->iT) * tr.iseT - expf((tp[c] - tr.tm) * tg.dist->iT) * tr.ist;
+            g = tg.dgrad(expf(l[c] - mx) * inv - tg.q(tr, c), ps) * scale;
+          }
+          dl[(int64_t)row * ldd + c] = g;
+        } else
         dl[(int64_t)row * ldd + c] = c < NC ? (expf(l[c] - mx) * inv - tg.q(tr, c)) * scale : 0.f;
+      }
     if (probs)
       for (int c = 0; c < NC; ++c) probs[(int64_t)row * NC + c] = expf(l[c] - mx) * inv;
   }
@@ -808,10 +838,15 @@ hipError_t f32_lrn_pool_bwd(const float* x, const float* dy, const uint8_t* arg,
 }
 
 hipError_t f32_softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale, float* dl,
-                          int ldd, float* stats, float* probs, float* work, hipStream_t st, float label_smoothing) {
+                          int ldd, float* stats, float* probs, float* work, hipStream_t st, float label_smoothing,
+                          const CeDistill* distill) {
   int nb = (B + 255) / 256;
   nb = nb < 1 ? 1 : (nb > CE_MAXB ? CE_MAXB : nb);
-  if (label_smoothing != 0.f) {
+  if (distill) {   // a CeDistill alone in the pack
+    if (label_smoothing != 0.f || !labels || !distill->t || NC < 1 || distill->ldt < NC) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((softmax_ce_f32_k<false, CeDistill>), dim3(nb), dim3(256), 0, st, logits, ldl, labels, B, NC, scale,
+                       dl, ldd, stats, probs, work, *distill);
+  } else if (label_smoothing != 0.f) {
     if (!labels) return hipErrorInvalidValue;
     hipLaunchKernelGGL((softmax_ce_f32_k<true, float>), dim3(nb), dim3(256), 0, st, logits, ldl, labels, B, NC, scale, dl,
                        ldd, stats, probs, work, label_smoothing);

@@ -254,9 +254,19 @@ hipError_t f32_lrn_pool_fwd(const float* x, int Nb, int H, int W, int C, int r, 
                             float* y, uint8_t* arg, hipStream_t st);
 hipError_t f32_lrn_pool_bwd(const float* x, const float* dy, const uint8_t* arg, int Nb, int H, int W, int C, int r,
                             float bias, float alpha, float beta, int relu_mask, float* dx, hipStream_t st);
+// Knowledge distillation (ce_stats.h DISTILL): the dense per-row soft target of a frozen teacher at a
+// temperature.  t: the teacher's fp32 logits [>= nb, ldt], ldt >= NC and not tied to the student's row
+// stride (columns >= NC are never read); alpha in [0, 1]: the weight of the soft part; T > 0: the
+// temperature, iT = 1 / T.  nullptr (here and on softmax_ce, mlp_head, ce_tail): the launch without it.
+// Never together with label_smoothing, labels2 / lam or a HeadDrop (hipErrorInvalidValue).
+struct CeDistill {
+  const float* t;
+  int ldt;
+  float alpha, T, iT;
+};
 hipError_t f32_softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale, float* dl,
                           int ldd, float* stats, float* probs, float* work, hipStream_t st,
-                          float label_smoothing = 0.f);
+                          float label_smoothing = 0.f, const CeDistill* distill = nullptr);
 hipError_t f32_prep_images(const uint8_t* src, const int64_t* idx, const int32_t* lab_src, int B, int HW, int Csrc,
                            int Cdst, float* out, int32_t* lab_out, hipStream_t st);
 
@@ -302,7 +312,7 @@ hipError_t lrn_pool_bwd(const bf16_t* x, const bf16_t* dP, const uint8_t* arg, i
 hipError_t softmax_ce(const float* logits, int ldl, const int32_t* labels, int B, int NC, float scale,
                       bf16_t* dlogits, int ldd, float* stats, float* probs, float* work, hipStream_t st,
                       int* defer_blocks = nullptr, float* dbias = nullptr, float label_smoothing = 0.f,
-                      const int32_t* labels2 = nullptr, const float* lam = nullptr);
+                      const int32_t* labels2 = nullptr, const float* lam = nullptr, const CeDistill* distill = nullptr);
 int softmax_ce_dbias_blocks(int B, int ldl);
 // Fused LeNet-5 dense head (mlp_head.hip): fc3/fc4/fc5 + softmax-CE (+ with dl:
 // the data-gradient chain dlogits -> dh4 -> dh3 -> dx).  Writes h3, h4, logits
@@ -343,7 +353,7 @@ struct HeadArgs {
   float* dbias;
 };
 hipError_t mlp_head(const HeadArgs& a, hipStream_t st, float label_smoothing = 0.f, const HeadDrop* drop = nullptr,
-                    const int32_t* labels2 = nullptr, const float* lam = nullptr);
+                    const int32_t* labels2 = nullptr, const float* lam = nullptr, const CeDistill* distill = nullptr);
 // blocks of one mlp_head launch (its per-block CE partials when defer_stats is set)
 int mlp_head_blocks(int nb);
 // the reference CNN's softmax_linear (192 -> nc <= 16) + softmax CE + its data gradient (masked by
@@ -366,7 +376,7 @@ struct TailArgs {
   float* dbias;
 };
 hipError_t ce_tail(const TailArgs& a, hipStream_t st, float label_smoothing = 0.f, const int32_t* labels2 = nullptr,
-                   const float* lam = nullptr);
+                   const float* lam = nullptr, const CeDistill* distill = nullptr);
 // What mlp_head / ce_tail call for the other label targets, each a translation unit of its own (the note
 // in mlp_head.hip); all are the gradient form only (dl required).  mlp_head_smooth.hip: label_smoothing != 0
 hipError_t ce_tail_smooth(const TailArgs& a, hipStream_t st, float label_smoothing);
@@ -379,6 +389,9 @@ hipError_t ce_tail_mix(const TailArgs& a, hipStream_t st, float label_smoothing,
                        const float* lam);
 hipError_t mlp_head_mix(const HeadArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2,
                         const float* lam, const HeadDrop* drop);
+// mlp_head_distill.hip: a teacher's soft target (CeDistill), alone in the pack
+hipError_t ce_tail_distill(const TailArgs& a, hipStream_t st, const CeDistill& distill);
+hipError_t mlp_head_distill(const HeadArgs& a, hipStream_t st, const CeDistill& distill);
 // Stand-alone dropout (dropout.hip) on a [nb, ld] bf16 buffer with n <= ld real columns, in place:
 // x = keep ? bf16(x * inv_keep) : +0, the keep bits of (seed, *step, layer) from dropout_rng.h.
 // Forward (on the activation) and backward (on the gradient: the bits are recomputed) are the same

@@ -199,6 +199,8 @@ DEV void drop_pack(const DropKey& k, float inv_keep, uint32_t m, uint32_t g, int
 // so the plain and the smoothed instantiation keep the names (and the code objects) they had before
 // the later members existed.  SMOOTH: label smoothing, eps opens the pack.  Two labels and a weight per
 // row (labels2 and lam behind eps; gradient form only): 8 more bytes read per row.
+// DISTILL (a CeDistill alone in the pack; gradient form only): the soft target of a teacher's logits,
+// 4 nc more bytes read per row (head_ce_body.h).
 // DROP (a HeadDrop closes the pack; gradient form only): dropout on h3 and h4 (dropout_rng.h).  The
 // masks are drawn where the activations are packed; h3 / h4 are stored dropped and scaled, so the
 // weight and bias gradients need nothing; the backward reads the bit off the packed activation
@@ -218,7 +220,8 @@ __global__ __launch_bounds__(64 * NW) void mlp_head_k(const bf16_t* __restrict__
   using TG = CeTarget<EPS...>;
   constexpr bool DROP = TG::DROP;
   static_assert(SMOOTH == TG::SMOOTH, "SMOOTH says whether eps opens the pack");
-  static_assert(GRADS || !(DROP || TG::MIX), "dropout and two labels are training quantities: the gradient form only");
+  static_assert(GRADS || !(DROP || TG::MIX || TG::DISTILL),
+                "dropout, two labels and a teacher are training quantities: the gradient form only");
   const TG tg(nc, eps...);
   __shared__ __attribute__((aligned(16))) bf16_t i3[R3 * S3];
   __shared__ __attribute__((aligned(16))) bf16_t i4[R4 * S4];
@@ -496,8 +499,9 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
                                                      float* __restrict__ work, int defer_stats,
                                                      float* __restrict__ dbias, EPS... eps) {
   using TG = CeTarget<EPS...>;
-  static_assert(SMOOTH == TG::SMOOTH && !TG::DROP && (GRADS || !TG::MIX),
-                "the smoothed instantiation takes eps, the mixed one (gradient form only) eps, labels2 and lam");
+  static_assert(SMOOTH == TG::SMOOTH && !TG::DROP && (GRADS || !(TG::MIX || TG::DISTILL)),
+                "the smoothed instantiation takes eps, the mixed one (gradient form only) eps, labels2 and lam, the "
+                "distilled one (gradient form only) a CeDistill");
   const TG tg(nc, eps...);
   __shared__ __attribute__((aligned(16))) bf16_t i5[16 * TD0];
   __shared__ __attribute__((aligned(16))) float bias5[LD3];
@@ -595,7 +599,7 @@ __global__ __launch_bounds__(64 * TNW) void ce_tail_k(const bf16_t* __restrict__
 
 
 // Launches.  The instantiations of each label target are a translation unit of their own
-// (mlp_head_smooth.hip, mlp_head_drop.hip, mlp_head_mix.hip, which include this text).  In one module
+// (mlp_head_smooth.hip, mlp_head_drop.hip, mlp_head_mix.hip, mlp_head_distill.hip, which include this text).  In one module
 // with the smoothed ones the plain mlp_head_k<true> came out of the compiler with other address
 // arithmetic and registers (4306 instead of 4290 instructions); apart, this file's code object is what
 // it was before they existed.
@@ -662,6 +666,19 @@ hipError_t mlp_head_mix(const HeadArgs& a, hipStream_t st, float label_smoothing
   return launch_head(mlp_head_k<true, NWAVE, 1, true, float, const int32_t*, const float*>, a, st, label_smoothing,
                      labels2, lam);
 }
+#elif defined(MNISTX_HEAD_DISTILL_TU)
+// a CeDistill alone in the pack
+hipError_t ce_tail_distill(const TailArgs& a, hipStream_t st, const CeDistill& distill) {
+  if (a.nb <= 0) return hipSuccess;
+  if (!a.dl || !distill.t) return hipErrorInvalidValue;   // a training quantity: the gradient form only
+  return launch_tail<true, false>(a, st, distill);
+}
+
+hipError_t mlp_head_distill(const HeadArgs& a, hipStream_t st, const CeDistill& distill) {
+  if (a.nb <= 0) return hipSuccess;
+  if (!a.dl || !distill.t) return hipErrorInvalidValue;
+  return launch_head(mlp_head_k<true, NWAVE, 1, false, CeDistill>, a, st, distill);
+}
 #else
 // waves per block (32 rows each): 2, or more when the block count would exceed the CE partial
 // slots; MNISTX_CE_TAIL_NW overrides (1, 2 or 4).  At B = 16384 2 waves (256 blocks) measured
@@ -680,8 +697,13 @@ int ce_tail_blocks(int nb) { const int r = 32 * ce_tail_nw(nb); return (nb + r -
 bool ce_tail_supported(int d0, int nc, int B) { return d0 == TD0 && nc > 0 && nc <= LD3 && B > 0 && ce_tail_blocks(B) <= CE_MAXB; }
 
 // the eval forms (dl == nullptr) write no bias gradient
-hipError_t ce_tail(const TailArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2, const float* lam) {
+hipError_t ce_tail(const TailArgs& a, hipStream_t st, float label_smoothing, const int32_t* labels2, const float* lam,
+                   const CeDistill* distill) {
   if ((labels2 != nullptr) != (lam != nullptr)) return hipErrorInvalidValue;
+  if (distill) {   // alone: no instantiation joins it with another target
+    if (labels2 || label_smoothing != 0.f) return hipErrorInvalidValue;
+    return ce_tail_distill(a, st, *distill);
+  }
   if (labels2) return ce_tail_mix(a, st, label_smoothing, labels2, lam);
   if (label_smoothing != 0.f) return ce_tail_smooth(a, st, label_smoothing);
   if (a.nb <= 0) return hipSuccess;
@@ -699,8 +721,12 @@ bool mlp_head_supported(int d0, int ld1, int ld2, int ld3, int n1, int n2, int n
 }
 
 hipError_t mlp_head(const HeadArgs& a, hipStream_t st, float label_smoothing, const HeadDrop* drop,
-                    const int32_t* labels2, const float* lam) {
+                    const int32_t* labels2, const float* lam, const CeDistill* distill) {
   if ((labels2 != nullptr) != (lam != nullptr)) return hipErrorInvalidValue;
+  if (distill) {
+    if (labels2 || drop || label_smoothing != 0.f) return hipErrorInvalidValue;
+    return mlp_head_distill(a, st, *distill);
+  }
   if (labels2) return mlp_head_mix(a, st, label_smoothing, labels2, lam, drop);
   if (drop) return mlp_head_drop(a, st, label_smoothing, *drop);
   if (label_smoothing != 0.f) return mlp_head_smooth(a, st, label_smoothing);

@@ -119,21 +119,45 @@ def two_label_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, labels2:
     return torch.where(lam < 1, lam * ca + (1 - lam) * cb, ca)
 
 
+def distillation_loss(logits: torch.Tensor, labels: torch.Tensor, teacher_logits: torch.Tensor, alpha: float,
+                      temperature: float) -> torch.Tensor:
+    """The knowledge-distillation loss per row: (1 - alpha) CE(labels) + alpha T^2 KL(q || pT), q the
+    teacher's softmax at the temperature T and pT the student's; the KL is summed per class
+    (``F.kl_div`` does so), so equal rows give exactly 0.  The teacher's logits carry no gradient."""
+    T = float(temperature)
+    hard = F.cross_entropy(logits, labels.long(), reduction="none")
+    q = F.softmax(teacher_logits.detach().to(logits.dtype) / T, dim=1)
+    soft = F.kl_div(F.log_softmax(logits / T, dim=1), q, reduction="none").sum(dim=1)
+    return (1.0 - alpha) * hard + (alpha * T * T) * soft
+
+
 def losses(spec: ModelSpec, params: Dict[str, torch.Tensor], logits: torch.Tensor,
            labels: torch.Tensor, label_smoothing: float = 0.0, labels2: Optional[torch.Tensor] = None,
-           lam: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+           lam: Optional[torch.Tensor] = None, teacher_logits: Optional[torch.Tensor] = None,
+           distill_alpha: float = 0.0, distill_temperature: float = 1.0) -> Dict[str, torch.Tensor]:
     """All entries of the reference 'losses' collection plus total_loss (``label_smoothing``:
     the training form of ``cross_entropy``, against (1 - eps) * onehot + eps / classes).
     ``labels2`` and ``lam`` (together): the mixup / CutMix loss mean(lam CE(labels) + (1 - lam) CE(labels2)),
-    the smoothing applied to both; a row with lam == 1 takes CE(labels) alone."""
+    the smoothing applied to both; a row with lam == 1 takes CE(labels) alone.
+    ``teacher_logits`` with ``distill_alpha`` > 0: the mean ``distillation_loss``; not together with the
+    other two forms."""
     if (labels2 is None) != (lam is None):
         raise ValueError(f"labels2 and lam come together, got {'labels2' if lam is None else 'lam'} alone")
+    from ..runtime.params import check_distill
+    distill_alpha, distill_temperature = check_distill(distill_alpha, distill_temperature)
+    distilled = teacher_logits is not None and distill_alpha > 0
+    if distilled and (label_smoothing != 0 or labels2 is not None):
+        raise ValueError(f"teacher_logits cannot be combined with "
+                         f"{'label_smoothing' if label_smoothing != 0 else 'labels2 / lam'}")
     out: Dict[str, torch.Tensor] = {}
     for L in spec.weights():
         if L.wd is not None:
             wgt = params[f"{L.name}/weights"]
             out[f"{L.name}/weight_loss"] = float(L.wd) * 0.5 * (wgt * wgt).sum()
-    if labels2 is not None:
+    if distilled:
+        out["cross_entropy"] = distillation_loss(logits, labels, teacher_logits, distill_alpha,
+                                                 distill_temperature).mean()
+    elif labels2 is not None:
         out["cross_entropy"] = two_label_cross_entropy(logits, labels, labels2, lam, label_smoothing).mean()
     else:
         out["cross_entropy"] = F.cross_entropy(logits, labels.long(), label_smoothing=label_smoothing)

@@ -168,10 +168,12 @@ class SoftmaxCrossEntropyFn(torch.autograd.Function):
     """Mean sparse softmax cross-entropy; the same kernel pass produces dlogits,
     the top-1 correct count and a non-finite flag (returned as ``stats``).  With
     ``label_smoothing`` the loss (and stats[0]) is the smoothed one; with ``labels2`` and ``lam`` it is
-    the two-label loss of mixup / CutMix."""
+    the two-label loss of mixup / CutMix; with ``teacher_logits`` and ``distill_alpha`` > 0 the distillation
+    loss (no gradient reaches the teacher's logits)."""
 
     @staticmethod
-    def forward(ctx, logits, labels, n_classes: int, label_smoothing: float = 0.0, labels2=None, lam=None):
+    def forward(ctx, logits, labels, n_classes: int, label_smoothing: float = 0.0, labels2=None, lam=None,
+                teacher_logits=None, distill_alpha: float = 0.0, distill_temperature: float = 1.0):
         logits = logits.float().contiguous()
         B = logits.shape[0]
         if (labels2 is None) != (lam is None):
@@ -179,7 +181,10 @@ class SoftmaxCrossEntropyFn(torch.autograd.Function):
         if labels2 is not None:
             labels2, lam = labels2.to(torch.int32).contiguous(), lam.to(torch.float32).contiguous()
         dl, stats = Fk.softmax_ce(logits, labels.to(torch.int32).contiguous(), n_classes, scale=1.0 / B,
-                                  label_smoothing=label_smoothing, labels2=labels2, lam=lam)
+                                  label_smoothing=label_smoothing, labels2=labels2, lam=lam,
+                                  teacher_logits=None if teacher_logits is None else
+                                  teacher_logits.detach().float().contiguous(),
+                                  distill_alpha=distill_alpha, distill_temperature=distill_temperature)
         ctx.save_for_backward(dl)
         ctx.mark_non_differentiable(stats)
         return stats[0] / B, stats
@@ -187,7 +192,7 @@ class SoftmaxCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dstats):
         (dl,) = ctx.saved_tensors
-        return dl.float() * dloss, None, None, None, None, None
+        return dl.float() * dloss, None, None, None, None, None, None, None, None
 
 
 class DropoutFn(torch.autograd.Function):
@@ -236,10 +241,13 @@ def lrn(x, r: int = 4, bias: float = 1.0, alpha: float = 0.001 / 9.0, beta: floa
     return LRNFn.apply(x, r, bias, alpha, beta)
 
 
-def softmax_cross_entropy(logits, labels, n_classes: int, label_smoothing: float = 0.0, labels2=None, lam=None):
+def softmax_cross_entropy(logits, labels, n_classes: int, label_smoothing: float = 0.0, labels2=None, lam=None,
+                          teacher_logits=None, distill_alpha: float = 0.0, distill_temperature: float = 1.0):
     """Returns (mean loss, stats f32[8]: [sum CE, #correct, nonfinite flag, ...]).  ``labels2`` / ``lam``
-    (together): the two-label loss mean(lam CE(labels) + (1 - lam) CE(labels2)) of mixup / CutMix."""
-    return SoftmaxCrossEntropyFn.apply(logits, labels, n_classes, label_smoothing, labels2, lam)
+    (together): the two-label loss mean(lam CE(labels) + (1 - lam) CE(labels2)) of mixup / CutMix.
+    ``teacher_logits`` with ``distill_alpha`` > 0: the distillation loss at ``distill_temperature``."""
+    return SoftmaxCrossEntropyFn.apply(logits, labels, n_classes, label_smoothing, labels2, lam, teacher_logits,
+                                       distill_alpha, distill_temperature)
 
 
 def dropout(x, step, seed: int, layer: int, p: float):

@@ -273,11 +273,15 @@ def lrn_bwd(x: torch.Tensor, dy: torch.Tensor, r: int, bias: float, alpha: float
 def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, n_classes: int, scale: Optional[float] = None,
                dlogits: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
                want_grad: bool = True, label_smoothing: float = 0.0, labels2: Optional[torch.Tensor] = None,
-               lam: Optional[torch.Tensor] = None):
+               lam: Optional[torch.Tensor] = None, teacher_logits: Optional[torch.Tensor] = None,
+               distill_alpha: float = 0.0, distill_temperature: float = 1.0):
     """Fused softmax-CE fwd+bwd.  Returns (dlogits bf16 [B, ld] or None, stats f32[8]).
     ``label_smoothing`` eps: loss and gradient against (1 - eps) * onehot + eps / n_classes.
     ``labels2`` (int32 [B]) and ``lam`` (fp32 [B]), together or not at all: the two-label target of mixup /
-    CutMix, lam * q(labels) + (1 - lam) * q(labels2) per row; the top-1 count stays that of ``labels``."""
+    CutMix, lam * q(labels) + (1 - lam) * q(labels2) per row; the top-1 count stays that of ``labels``.
+    ``teacher_logits`` (fp32 [>= B, ldt], ldt >= n_classes: a frozen teacher's logits) with ``distill_alpha``
+    in (0, 1] and ``distill_temperature`` T > 0: knowledge distillation, the loss (1 - alpha) CE(labels) +
+    alpha T^2 KL(softmax(teacher / T) || softmax(logits / T)) per row; not with the two forms above."""
     if (labels2 is None) != (lam is None):
         raise ValueError(f"labels2 and lam come together, got {'labels2' if lam is None else 'lam'} alone")
     B, ld = logits.shape
@@ -288,7 +292,9 @@ def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, n_classes: int, scale
     if want_grad and dlogits is None:
         dlogits = torch.empty(B, ld, dtype=torch.bfloat16, device=logits.device)
     kernels().softmax_ce(logits, ld, labels, B, n_classes, scale, dlogits if want_grad else None, ld, stats, None,
-                         label_smoothing=label_smoothing, labels2=labels2, lam=lam)
+                         label_smoothing=label_smoothing, labels2=labels2, lam=lam, teacher_logits=teacher_logits,
+                         teacher_ld=0 if teacher_logits is None else teacher_logits.shape[-1],
+                         distill_alpha=distill_alpha, distill_temperature=distill_temperature)
     return dlogits, stats
 
 

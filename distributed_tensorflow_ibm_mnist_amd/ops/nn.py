@@ -71,17 +71,25 @@ class Linear(nn.Module):
 
 
 class SoftmaxCrossEntropy(nn.Module):
-    def __init__(self, n_classes: int, label_smoothing: float = 0.0):
+    def __init__(self, n_classes: int, label_smoothing: float = 0.0, distill_alpha: float = 0.0,
+                 distill_temperature: float = 1.0):
         super().__init__()
         if not 0 <= float(label_smoothing) < 1:      # NaN fails both comparisons
             raise ValueError(f"label_smoothing must be finite with 0 <= label_smoothing < 1, got {label_smoothing}")
+        from ..runtime.params import check_distill
+        self.distill_alpha, self.distill_temperature = check_distill(distill_alpha, distill_temperature)
+        if self.distill_alpha > 0 and float(label_smoothing) > 0:
+            raise ValueError(f"distill_alpha ({distill_alpha}) cannot be combined with label_smoothing "
+                             f"({label_smoothing})")
         self.n_classes, self.label_smoothing = n_classes, float(label_smoothing)
         self.last_stats: Optional[torch.Tensor] = None
 
-    def forward(self, logits, y, y2=None, lam=None):
+    def forward(self, logits, y, y2=None, lam=None, teacher_logits=None):
         """``y2`` (a second label per row) and ``lam`` (the weight of ``y``), together or not at all:
-        the loss of mixup / CutMix, mean(lam CE(y) + (1 - lam) CE(y2))."""
-        loss, stats = A.softmax_cross_entropy(logits, y, self.n_classes, self.label_smoothing, y2, lam)
+        the loss of mixup / CutMix, mean(lam CE(y) + (1 - lam) CE(y2)).  ``teacher_logits`` (with the
+        module's ``distill_alpha`` > 0): the distillation loss against a frozen teacher's logits."""
+        loss, stats = A.softmax_cross_entropy(logits, y, self.n_classes, self.label_smoothing, y2, lam,
+                                              teacher_logits, self.distill_alpha, self.distill_temperature)
         self.last_stats = stats
         return loss
 

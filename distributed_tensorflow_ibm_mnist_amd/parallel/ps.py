@@ -1275,6 +1275,9 @@ class PSWorkerReplica:
     def _compute(self) -> None:
         """forward + CE + backward + L2 terms + stats: no communication, so one hipGraph."""
         net = self.net
+        teacher = getattr(self.base, "teacher", None)
+        if teacher is not None:       # knowledge distillation: the worker's own frozen teacher (Replica._body)
+            teacher.forward(net.B)
         net.forward(defer_head=True)
         net.loss_and_grad()
         net.backward()

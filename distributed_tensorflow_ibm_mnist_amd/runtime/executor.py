@@ -391,6 +391,28 @@ def _weight_pads(spec: ModelSpec) -> Dict[str, Tuple[int, int]]:
     return pads
 
 
+def adopt_x0(x0: Optional[torch.Tensor], shape, dtype, dev) -> torch.Tensor:
+    """An executor's input buffer: a fresh zeroed one, or the given one after checking that it fits."""
+    if x0 is None:
+        return torch.zeros(*shape, dtype=dtype, device=dev)
+    if tuple(x0.shape) != tuple(shape) or x0.dtype != dtype or x0.device != dev or not x0.is_contiguous():
+        raise ValueError(f"x0 must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got "
+                         f"{x0.dtype} {tuple(x0.shape)} on {x0.device}")
+    return x0
+
+
+def distill_keywords(opt: OptConfig, teacher_logits: Optional[torch.Tensor]) -> dict:
+    """The teacher keywords of the softmax-CE bindings for a training launch under ``opt``; {} when
+    distillation is off.  On without a teacher's logits is an error, never a silent plain loss."""
+    if not opt.distill_alpha > 0:
+        return {}
+    if teacher_logits is None:
+        raise RuntimeError(f"distill_alpha={opt.distill_alpha} needs the net's teacher_logits (runtime/teacher.py "
+                           f"Teacher.attach), which is not set")
+    return dict(teacher_logits=teacher_logits, teacher_ld=teacher_logits.shape[1], distill_alpha=opt.distill_alpha,
+                distill_temperature=opt.distill_temperature)
+
+
 class HipNet:
     """One model replica on one GPU: buffers + kernels for fwd / bwd / update."""
 
@@ -401,7 +423,9 @@ class HipNet:
     def __init__(self, spec: ModelSpec, batch: int, device, init: Dict[str, torch.Tensor],
                  opt: Optional[OptConfig] = None, fuse_convpool: bool = True, overlap_backward: bool = False,
                  fuse_head: bool = True, fuse_lrnpool: Optional[bool] = None, fused_lenet_bwd: bool = True,
-                 fold_lrn_fwd: bool = False):
+                 fold_lrn_fwd: bool = False, x0: Optional[torch.Tensor] = None):
+        """``x0``: an input buffer to adopt instead of allocating one (a distillation teacher reads its
+        student's batch in place, runtime/teacher.py); [batch, H, W, C] of the executor's input dtype."""
         dev = torch.device(device)
         if fuse_lrnpool is None:
             fuse_lrnpool = os.environ.get("MNISTX_FUSE_LRNPOOL", "1") != "0"
@@ -416,8 +440,12 @@ class HipNet:
         self.fp = FlatParams.build(specs, init, dev, pads)
         self.fp.init_slots(self.opt)
         H, W = spec.input_hw
-        self.x0 = _bf16(batch, H, W, spec.in_channels, device=dev)
+        self.x0 = adopt_x0(x0, (batch, H, W, spec.in_channels), torch.bfloat16, dev)
         self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+        # knowledge distillation (opt.distill_alpha > 0): the frozen teacher's fp32 logits [>= batch, ld] the
+        # training loss reads, set by whoever runs the teacher (runtime/teacher.py); a fixed buffer, so a
+        # captured step replays it.  Eval paths never read it.
+        self.teacher_logits: Optional[torch.Tensor] = None
         # mixup / CutMix: the second label and the weight of the first per row, written by the loader's
         # mix launch (DeviceLoader(out_labels2=, out_lam=)) and read by the training loss alone
         self.labels2: Optional[torch.Tensor] = None
@@ -654,6 +682,10 @@ class HipNet:
         self.fp.enable_transposed({l5.wname: (16, 192)})
         return i
 
+    def _distill_kw(self) -> dict:
+        """The softmax-CE bindings' teacher keywords of a training launch ({}: distillation is off)."""
+        return distill_keywords(self.opt, self.teacher_logits)
+
     def _run_head(self, nb: int, scale: float, grads: bool, stats: torch.Tensor) -> None:
         i = self.head
         # training statistics: the per-block CE partials are combined by this step's
@@ -668,6 +700,9 @@ class HipNet:
                         drop_layer3=self.layers[i].idx, drop_layer4=self.layers[i + 1].idx)
         # and so do the two labels of mixup / CutMix: fixed buffers, so a captured step replays them
         mix = dict(labels2=self.labels2, lam=self.mix_lam) if (grads and self.opt.mix) else {}
+        # and so does the teacher's soft target (it shares the slot of the mix keywords: never both)
+        if grads and self.opt.distill_alpha > 0:
+            mix = self._distill_kw()
         if self.head_kind == "tail":
             l5 = self.layers[i]
             K = kernels()
@@ -805,7 +840,7 @@ class HipNet:
         # training statistics deferred to this step's finalize_k, as for the fused head
         ld = self.logits.shape[1]
         nblk = kernels().softmax_ce_dbias_blocks(nb, ld)
-        mix = dict(labels2=self.labels2, lam=self.mix_lam) if self.opt.mix else {}
+        mix = dict(labels2=self.labels2, lam=self.mix_lam) if self.opt.mix else self._distill_kw()
         self._ce_defer_blocks = kernels().softmax_ce(
             self.logits, ld, self.labels, nb, self.n_classes,
             (1.0 / nb) if scale is None else scale, self.dlogits, ld, self.stats,

@@ -33,7 +33,7 @@ import torch
 from ..models.spec import Conv, Dense, LRN, MaxPool, ModelSpec
 from ..ops import functional as Fk
 from ..ops._ext import kernels
-from .executor import HipNet
+from .executor import HipNet, adopt_x0, distill_keywords
 from .params import FlatParams, OptConfig
 
 
@@ -277,10 +277,10 @@ class HipNetF32:
     precision = "fp32"
 
     def __init__(self, spec: ModelSpec, batch: int, device, init: Dict[str, torch.Tensor],
-                 opt: Optional[OptConfig] = None, fuse: bool = True):
+                 opt: Optional[OptConfig] = None, fuse: bool = True, x0: Optional[torch.Tensor] = None):
         """``fuse``: conv1 + pool1 and LRN + pool runs as one kernel each where the kernels
         cover the geometry (ConvPoolF, LRNPoolF); False keeps the reference's layer-by-layer
-        graph (tests compare the two)."""
+        graph (tests compare the two).  ``x0``: an fp32 input buffer to adopt (HipNet)."""
         dev = torch.device(device)
         if opt is not None and opt.mix:     # the two-label loss is in the bf16 softmax-CE kernels alone
             raise ValueError("mixup_alpha / cutmix_alpha are not supported by the fp32 executor (--precision=fp32): "
@@ -299,8 +299,9 @@ class HipNetF32:
         self.fp = FlatParams.build(specs, init, dev, bf16_copies=False)   # kernels read the fp32 masters
         self.fp.init_slots(self.opt)
         H, W = spec.input_hw
-        self.x0 = _f32(batch, H, W, spec.in_channels, device=dev)
+        self.x0 = adopt_x0(x0, (batch, H, W, spec.in_channels), torch.float32, dev)
         self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.teacher_logits: Optional[torch.Tensor] = None     # knowledge distillation (HipNet.teacher_logits)
         self.layers: List[_L] = []
         x, in_relu = self.x0, False
         skip = -1
@@ -378,7 +379,8 @@ class HipNetF32:
         nb = self.B if nb is None else nb
         kernels().f32_softmax_ce(self.logits, self.logits.shape[1], self.labels, nb, self.n_classes,
                                  (1.0 / nb) if scale is None else scale, self.dlogits, self.logits.shape[1],
-                                 self.stats, None, self.ce_work, label_smoothing=self.opt.label_smoothing)
+                                 self.stats, None, self.ce_work, label_smoothing=self.opt.label_smoothing,
+                                 **distill_keywords(self.opt, self.teacher_logits))
 
     def backward(self, nb: Optional[int] = None) -> None:
         nb = self.B if nb is None else nb

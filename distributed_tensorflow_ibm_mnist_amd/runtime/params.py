@@ -32,6 +32,26 @@ LAYERWISE_RULES = ("lars", "lamb")
 LR_SCHEDULES = ("staircase", "polynomial", "cosine")
 
 
+def check_distill(alpha, temperature) -> Tuple[float, float]:
+    """``distill_alpha`` (finite, 0 <= alpha <= 1) and ``distill_temperature`` (finite, > 0, its square
+    finite in fp32) as floats; anything else is a ValueError naming key and value."""
+    out = []
+    for key, v in (("distill_alpha", alpha), ("distill_temperature", temperature)):
+        try:
+            if isinstance(v, bool):
+                raise ValueError
+            out.append(float(v))
+        except (TypeError, ValueError):
+            raise ValueError(f"{key} must be a number, got {v!r}") from None
+    a, t = out
+    if not 0 <= a <= 1:       # NaN fails both comparisons
+        raise ValueError(f"distill_alpha must be finite with 0 <= distill_alpha <= 1, got {a}")
+    if not (math.isfinite(t) and t > 0 and t * t <= 3.4028234663852886e38 and 1.0 / t <= 3.4028234663852886e38
+            and t >= 1.1754943508222875e-38):
+        raise ValueError(f"distill_temperature must be finite and > 0 with its square finite in fp32, got {t}")
+    return a, t
+
+
 @dataclasses.dataclass
 class OptConfig:
     lr0: float = 0.1
@@ -82,10 +102,18 @@ class OptConfig:
     # the hard labels.  The draw itself is the loader's (MixConfig); this flag only says that the
     # training loss reads the two buffers.  False: nothing is allocated, the launches are today's.
     mix: bool = False
+    # knowledge distillation: the training loss is (1 - alpha) * CE(labels) + alpha * T^2 * KL(q || pT) with q
+    # the softmax of a frozen teacher's logits at the temperature T and pT the student's (the softmax-CE
+    # kernels' distilled instantiations, which read the net's ``teacher_logits`` buffer); eval paths keep
+    # the plain cross-entropy.  0: off, nothing extra is launched.  Not combined with label_smoothing,
+    # mix or dropout: those need further instantiations of the fused head.
+    distill_alpha: float = 0.0
+    distill_temperature: float = 2.0
 
     def __post_init__(self):
         if not isinstance(self.mix, (bool,)):
             raise ValueError(f"mix must be a bool, got {self.mix!r}")
+        self.distill_alpha, self.distill_temperature = check_distill(self.distill_alpha, self.distill_temperature)
         from ..ops.dropout import check_rate, check_seed
         self.dropout = check_rate(self.dropout, "dropout")
         self.dropout_seed = check_seed(self.dropout_seed, "dropout_seed")
@@ -99,6 +127,11 @@ class OptConfig:
         if not 0 <= self.label_smoothing < 1:     # NaN fails both comparisons
             raise ValueError(f"label_smoothing must be finite with 0 <= label_smoothing < 1, "
                              f"got {self.label_smoothing}")
+        if self.distill_alpha > 0:
+            for key, on in (("label_smoothing", self.label_smoothing > 0), ("mix", self.mix), ("dropout", self.dropout > 0)):
+                if on:
+                    raise ValueError(f"distill_alpha ({self.distill_alpha}) cannot be combined with {key} "
+                                     f"({getattr(self, key)})")
         self.schedule = str(self.schedule).lower()
         if self.schedule not in LR_SCHEDULES:
             raise ValueError(f"schedule must be one of {'|'.join(LR_SCHEDULES)}, got {self.schedule!r}")
@@ -139,7 +172,7 @@ class OptConfig:
     @staticmethod
     def from_spec(spec, decay_steps: int, decay_rate: float, ema: float = 0.9999,
                   label_smoothing: float = 0.0, dropout: float = 0.0, dropout_seed: int = 0,
-                  mix: bool = False) -> "OptConfig":
+                  mix: bool = False, distill_alpha: float = 0.0, distill_temperature: float = 2.0) -> "OptConfig":
         """From a parameter-manager ``OptimizerSpec`` (which does not carry ``label_smoothing`` or
         the dropout keys: the caller passes ``getLabelSmoothing()``, ``getDropout()`` and the seed)."""
         lr = spec.learning_rate
@@ -157,7 +190,8 @@ class OptConfig:
                          warmup_steps=getattr(spec, "warmup_steps", 0),
                          total_steps=getattr(spec, "lr_total_steps", 0),
                          lr_end=getattr(spec, "lr_end", 0.0), lr_power=getattr(spec, "lr_power", 1.0),
-                         label_smoothing=label_smoothing, dropout=dropout, dropout_seed=dropout_seed, mix=mix)
+                         label_smoothing=label_smoothing, dropout=dropout, dropout_seed=dropout_seed, mix=mix,
+                         distill_alpha=distill_alpha, distill_temperature=distill_temperature)
 
     @property
     def scheduled(self) -> bool:

@@ -131,7 +131,8 @@ def _in_top1(logits: torch.Tensor, lab: torch.Tensor) -> torch.Tensor:
 
 class TorchNet:
     def __init__(self, spec: ModelSpec, batch: int, device, init: Dict[str, torch.Tensor],
-                 opt: Optional[OptConfig] = None, autocast: Optional[bool] = None):
+                 opt: Optional[OptConfig] = None, autocast: Optional[bool] = None, x0: Optional[torch.Tensor] = None):
+        """``x0``: an input buffer to adopt instead of allocating one (HipNet)."""
         dev = torch.device(device)
         self.spec, self.B, self.device = spec, batch, dev
         self.opt = opt or OptConfig()
@@ -145,8 +146,14 @@ class TorchNet:
         H, W = spec.input_hw
         self.autocast = (dev.type == "cuda") if autocast is None else autocast
         xdt = torch.bfloat16 if dev.type == "cuda" else torch.float32
-        self.x0 = torch.zeros(batch, H, W, spec.in_channels, dtype=xdt, device=dev)
+        if x0 is not None and (tuple(x0.shape) != (batch, H, W, spec.in_channels) or x0.dtype != xdt or x0.device != dev):
+            raise ValueError(f"x0 must be a {xdt} tensor of shape {(batch, H, W, spec.in_channels)} on {dev}, got "
+                             f"{x0.dtype} {tuple(x0.shape)} on {x0.device}")
+        self.x0 = torch.zeros(batch, H, W, spec.in_channels, dtype=xdt, device=dev) if x0 is None else x0
         self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+        # knowledge distillation (opt.distill_alpha > 0): the teacher's logits [>= batch, >= classes] that the
+        # training loss reads (HipNet.teacher_logits)
+        self.teacher_logits: Optional[torch.Tensor] = None
         # mixup / CutMix: the loader's second labels and weights, read by the training loss alone
         self.labels2: Optional[torch.Tensor] = None
         self.mix_lam: Optional[torch.Tensor] = None
@@ -198,7 +205,12 @@ class TorchNet:
             self.forward(nb, grad=True)
         lab = self.labels[:nb].long()
         # the training loss (and its cross_entropy scalar) is the smoothed one; eval_batch is not
-        if self.opt.mix:    # torch_ref.losses' two-label form, as a sum over the rows
+        if self.opt.distill_alpha > 0:      # torch_ref.losses' distilled form, as a sum over the rows
+            if self.teacher_logits is None:
+                raise RuntimeError(f"distill_alpha={self.opt.distill_alpha} needs the net's teacher_logits, which is not set")
+            loss = torch_ref.distillation_loss(self._logits, lab, self.teacher_logits[:nb, :self.n_classes],
+                                               self.opt.distill_alpha, self.opt.distill_temperature).sum()
+        elif self.opt.mix:    # torch_ref.losses' two-label form, as a sum over the rows
             loss = torch_ref.two_label_cross_entropy(self._logits, lab, self.labels2[:nb], self.mix_lam[:nb],
                                                      self.opt.label_smoothing).sum()
         else:

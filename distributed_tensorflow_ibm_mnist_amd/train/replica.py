@@ -22,16 +22,18 @@ from ..parallel.dp import DataParallel
 from ..runtime.params import FlatParams, OptConfig
 
 
-def build_net(impl: str, spec: ModelSpec, batch: int, device, init, opt: OptConfig, precision: str = "bf16"):
+def build_net(impl: str, spec: ModelSpec, batch: int, device, init, opt: OptConfig, precision: str = "bf16", x0=None):
+    """``x0``: an input buffer the executor adopts instead of allocating one (runtime/teacher.py)."""
+    kw = {} if x0 is None else {"x0": x0}
     if impl == "hip" and precision == "fp32":
         from ..runtime.executor_f32 import HipNetF32
-        return HipNetF32(spec, batch, device, init, opt)
+        return HipNetF32(spec, batch, device, init, opt, **kw)
     if impl == "hip":
         assert precision == "bf16", f"unknown precision {precision!r}"
         from ..runtime.executor import HipNet
-        return HipNet(spec, batch, device, init, opt)
+        return HipNet(spec, batch, device, init, opt, **kw)
     from ..runtime.torchnet import TorchNet
-    return TorchNet(spec, batch, device, init, opt)
+    return TorchNet(spec, batch, device, init, opt, **kw)
 
 
 def state_tensors(net, include_momentum: bool = True) -> Dict[str, np.ndarray]:
@@ -101,13 +103,23 @@ class Replica:
                  eval_images: Optional[torch.Tensor] = None, eval_labels: Optional[torch.Tensor] = None,
                  seed: int = 0, shard: bool = True, use_graph: bool = True, bucket_mb: float = 4.0,
                  group=None, standalone: bool = False, fused_input=False, precision: str = "bf16",
-                 dp_graph: bool = False, augment=None, mix=None, log=print):
+                 dp_graph: bool = False, augment=None, mix=None, log=print, teacher=None):
         """``augment``: a ``data.augment.AugmentConfig``; when any of its amounts is non-zero the
         training batches (and only those) are shifted / rotated / zoomed on the device.
         ``mix``: a ``data.mix.MixConfig``; when it mixes anything, ``opt.mix`` must be set (the net then
-        holds ``labels2`` / ``mix_lam``) and the training batches are mixed by the loader."""
+        holds ``labels2`` / ``mix_lam``) and the training batches are mixed by the loader.
+        ``teacher``: knowledge distillation -- a callable ``(student net, impl, precision) -> Teacher``
+        (``runtime.teacher.TeacherSource``), called once the net exists; ``opt.distill_alpha`` must be > 0.
+        The teacher's forward then runs in the step body, before the student's step."""
         self.spec, self.impl, self.B, self.device = spec, impl, batch, torch.device(device)
         self.net = build_net(impl, spec, batch, self.device, init, opt, precision)
+        self.teacher = None
+        if teacher is not None:
+            if not opt.distill_alpha > 0:
+                raise ValueError("a teacher needs OptConfig(distill_alpha > 0): the training loss reads its logits")
+            self.teacher = teacher(self.net, impl, precision)
+        elif opt.distill_alpha > 0:
+            raise ValueError(f"distill_alpha={opt.distill_alpha} needs a teacher (distill_from)")
         # standalone: a parameter-server worker (no data-parallel group of its own)
         dp_on = dist.is_initialized() and not standalone
         self.world = dist.get_world_size(group) if dp_on else 1
@@ -131,6 +143,10 @@ class Replica:
             # the first fused conv can only gather unmixed dataset rows
             log(f"mixup / CutMix is on: input mode {mode!r} -> 'prep' (the mix kernel works on the input buffer)")
             mode = "prep"
+        if self.teacher is not None and mode != "prep":
+            # the teacher reads the input buffer, which the gathering first conv never writes
+            log(f"distillation is on: input mode {mode!r} -> 'prep' (the teacher reads the input buffer)")
+            mode = "prep"
         # eligibility first: a model that cannot gather (3-channel input, fp32 executor) never
         # gets a normalised bf16 copy of the whole split built for nothing
         fused_in = (impl == "hip" and mode != "prep" and getattr(self.net, "can_gather_input", lambda: True)()
@@ -148,9 +164,15 @@ class Replica:
         self._eval_acc = None      # obs.eval_metrics.EvalAccumulator of evaluate(metrics=True), made on first use
         self.global_step = 0
         self.examples_per_step = batch * self.world
+        if self.teacher is not None and self.eval_ds is not None:
+            ev = self.teacher.evaluate(self.eval_ds)
+            log(f"distillation teacher {self.teacher.spec.name}: test accuracy {ev['accuracy']:.4f} "
+                f"(loss {ev['loss']:.4f}, {ev['examples']} examples)")
 
     # ------------------------------------------------------------------ steps
     def _body(self) -> None:
+        if self.teacher is not None:      # the soft targets of the batch the loader just wrote
+            self.teacher.forward(self.B)
         self.dp.train_step()
 
     def step(self) -> None:

@@ -110,12 +110,15 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
                               dropout=pm.getDropout(),
                               dropout_seed=pm.getDropoutSeed(FLAGS.seed) + (cl.rank if cl.mode == "dp" else 0),
                               # mixup / CutMix: the training loss takes two labels (the draw is the loader's)
-                              mix=pm.getMix(FLAGS.seed).enabled)
+                              mix=pm.getMix(FLAGS.seed).enabled,
+                              **_distill_opt(pm.getDistill()))
     # training-input augmentation: drawn per (augment_seed, stream position), so sharded ranks differ
     # without a per-rank seed (an unsharded loader offsets the seed itself, as it does for the shuffle)
     augment = pm.getAugment(FLAGS.seed)
     # mixup / CutMix: drawn per (mix_seed, stream position) too
     mix = pm.getMix(FLAGS.seed)
+    # knowledge distillation: every rank / PS worker loads the frozen teacher itself (nothing is broadcast)
+    teacher = _teacher_source(pm.getDistill())
     init = torch_ref.init_params(spec, seed=FLAGS.seed)
     if cl.mode == "ps" and cl.job_name == "ps":
         from ..ckpt.saver import Saver, latest_checkpoint
@@ -147,9 +150,10 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
                    seed=FLAGS.seed, shard=not FLAGS.no_shard, use_graph=FLAGS.hip_graph,
                    bucket_mb=FLAGS.bucket_mb, group=dp_group if cl.mode == "dp" else None,
                    fused_input=True if FLAGS.fused_input else getattr(FLAGS, "input_mode", "prep"), precision=getattr(FLAGS, "precision", "bf16"),
-                   dp_graph=getattr(FLAGS, "hip_graph_dp", False), augment=augment, mix=mix, log=log) \
+                   dp_graph=getattr(FLAGS, "hip_graph_dp", False), augment=augment, mix=mix, log=log,
+                   **({"teacher": teacher} if teacher is not None else {})) \
         if cl.mode != "ps" else _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS,
-                                         augment, log, mix)
+                                         augment, log, mix, teacher)
     replica = base
     if cl.mode == "ps":
         from ..parallel.ps import PSWorkerReplica
@@ -215,8 +219,20 @@ def _train(FLAGS, cl: Cluster, max_steps, test_interval, batch_size, impl, log) 
     return res
 
 
+def _distill_opt(d) -> dict:
+    """The OptConfig keywords of a ``parameter_mgr.DistillSpec`` ({}: off, the defaults stay)."""
+    return dict(distill_alpha=d.alpha, distill_temperature=d.temperature) if d.enabled else {}
+
+
+def _teacher_source(d):
+    if not d.enabled:
+        return None
+    from ..runtime.teacher import TeacherSource
+    return TeacherSource(d.ckpt_dir, d.model, d.use_ema)
+
+
 def _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev, FLAGS, augment=None, log=print,
-             mix=None):
+             mix=None, teacher=None):
     """A PS-mode worker: own input stream (reference P3: no sharding), no DP group.  It owns its
     loader and its loss, so it augments and mixes its own inputs; the servers never see them."""
     if mix is not None and mix.enabled:
@@ -227,4 +243,5 @@ def _ps_base(spec, impl, batch_size, cl, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev
         augment = augment.with_seed((augment.seed + 7919 * cl.task_id) % (1 << 63))
     return Replica(spec, impl, batch_size, cl.device, init, opt, x_tr, y_tr, c_tr, x_ev, y_ev,
                    seed=FLAGS.seed + 7919 * cl.task_id, shard=False, use_graph=False, bucket_mb=FLAGS.bucket_mb,
-                   standalone=True, precision=getattr(FLAGS, "precision", "bf16"), augment=augment, mix=mix, log=log)
+                   standalone=True, precision=getattr(FLAGS, "precision", "bf16"), augment=augment, mix=mix, log=log,
+                   **({"teacher": teacher} if teacher is not None else {}))

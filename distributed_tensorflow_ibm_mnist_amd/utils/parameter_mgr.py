@@ -77,6 +77,11 @@ DEFAULTS: Dict[str, Any] = {
     "cutmix_alpha": 0.0,         # ... CutMix with the box area from Beta(a, a) (0.1..8); 0: off; both set: one of the two per entry
     "mix_prob": 1.0,             # ... probability that an entry is mixed at all (0..1)
     "mix_seed": None,            # seed of the counter-based mixing draws; None: the run's seed
+    "distill_from": "",          # knowledge distillation: the frozen teacher's checkpoint directory; '': off
+    "distill_model": "",         # ... the teacher's registry name (required with distill_from)
+    "distill_alpha": None,       # ... weight of the soft part of the loss, 0..1; None: 0.5 with distill_from, else 0
+    "distill_temperature": 2.0,  # ... the temperature T > 0 of both softmaxes
+    "distill_use_ema": 0,        # ... 1: the teacher's ExponentialMovingAverage shadows
     "train_data": ["synthetic://60000"],
     "test_data": ["synthetic://10000?seed=1"],
     "val_data": ["synthetic://10000?seed=2"],
@@ -163,7 +168,8 @@ FLAG_KEYS = ("max_steps", "test_interval", "batch_size", "base_lr", "lr_decay", 
              "adagrad_initial_accumulator", "clip_norm", "lars_eta", "lr_schedule", "warmup_steps",
              "lr_total_steps", "lr_end", "lr_power", "label_smoothing", "dropout", "dropout_seed",
              "augment_shift", "augment_rotate", "augment_scale", "augment_seed", "augment_elastic_alpha",
-             "augment_elastic_sigma", "mixup_alpha", "cutmix_alpha", "mix_prob", "mix_seed")
+             "augment_elastic_sigma", "mixup_alpha", "cutmix_alpha", "mix_prob", "mix_seed", "distill_from",
+             "distill_model", "distill_alpha", "distill_temperature", "distill_use_ema")
 ADAPTIVE_OPTIMIZERS = ("adam", "rmsprop", "adagrad")
 LAYERWISE_OPTIMIZERS = ("lars", "lamb")   # layer-wise trust ratios on top of momentum / Adam
 
@@ -368,6 +374,51 @@ def getMix(default_seed: int = 0):
     The workers own their loader and their loss, so parameter-server mode takes the keys as they are."""
     from ..data.mix import MixConfig
     return MixConfig(getMixupAlpha(), getCutmixAlpha(), getMixProb(), getMixSeed(default_seed))
+
+
+@dataclasses.dataclass(frozen=True)
+class DistillSpec:
+    """What ``getDistill()`` returns; ``enabled``: a teacher is loaded and the loss reads its logits."""
+    ckpt_dir: str
+    model: str
+    alpha: float
+    temperature: float
+    use_ema: bool
+
+    @property
+    def enabled(self) -> bool:
+        return bool(self.ckpt_dir) and self.alpha > 0
+
+
+def getDistill() -> DistillSpec:
+    """The five distillation keys.  ``distill_from`` '' is off (the other keys are still checked);
+    ``distill_alpha`` unset is 0.5 with a teacher.  The workers own their loss and each loads the
+    teacher itself, so data-parallel and parameter-server mode take the keys as they are.  Together
+    with label_smoothing, mixup / CutMix or dropout it is refused (the fused head has no such form)."""
+    from ..runtime.params import check_distill
+    src, model = get("distill_from"), get("distill_model")
+    for key, v in (("distill_from", src), ("distill_model", model)):
+        if v is not None and not isinstance(v, str):
+            raise ValueError(f"{key} must be a string, got {v!r}")
+    src, model = src or "", model or ""
+    a = get("distill_alpha")
+    alpha, T = check_distill((0.5 if src else 0.0) if a is None else a, get("distill_temperature"))
+    ema = get("distill_use_ema")
+    if isinstance(ema, str) or ema not in (0, 1, False, True):
+        raise ValueError(f"distill_use_ema must be 0 or 1, got {ema!r}")
+    if src and not model:
+        raise ValueError(f"distill_model is required with distill_from ({src!r})")
+    if model and not src:
+        raise ValueError(f"distill_model ({model!r}) needs distill_from")
+    if alpha > 0 and not src:
+        raise ValueError(f"distill_alpha ({alpha}) needs distill_from")
+    spec = DistillSpec(src, model, alpha, T, bool(ema))
+    if spec.enabled:
+        for key, on in (("label_smoothing", getLabelSmoothing() > 0), ("mixup_alpha", getMixupAlpha() > 0),
+                        ("cutmix_alpha", getCutmixAlpha() > 0), ("dropout", getDropout() > 0)):
+            if on:
+                raise ValueError(f"distill_from ({src!r}) cannot be combined with {key} ({get(key)})")
+    return spec
 
 
 def check_ps_dropout(job_name: str, log=print) -> None:

@@ -79,6 +79,15 @@ flags.DEFINE_float("mixup_alpha", -1, "training batches only: mixup of every ent
 flags.DEFINE_float("cutmix_alpha", -1, "training batches only: CutMix, a box of the partner pasted in, its area from "
                    "Beta(a, a), 0.1..8 (0.0: off; -1: unset); with mixup_alpha also set each entry takes one of the two")
 flags.DEFINE_float("mix_prob", -1, "probability that a batch entry is mixed at all, 0..1 (-1: unset, 1.0)")
+flags.DEFINE_string("distill_from", "", "knowledge distillation: the checkpoint directory of a frozen teacher whose "
+                    "logits at a temperature become a soft target of the training loss ('': off)")
+flags.DEFINE_string("distill_model", "", "the teacher's registry name (required with --distill_from); its input "
+                    "channels, input size and class count must be the student's")
+flags.DEFINE_float("distill_alpha", -1, "weight of the soft part: loss = (1 - a) CE + a T^2 KL(teacher || student), "
+                   "0..1 (-1: unset, 0.5 with --distill_from)")
+flags.DEFINE_float("distill_temperature", -1, "the temperature T > 0 of the teacher's and the student's softmax in "
+                   "the soft part (-1: unset, 2.0)")
+flags.DEFINE_integer("distill_use_ema", -1, "1: restore the teacher's ExponentialMovingAverage shadows (-1: unset, 0)")
 flags.DEFINE_integer("mix_seed", -1, "seed of the mixing draws (-1: unset, the run's --seed); a draw is a pure function "
                      "of (seed, stream position), so a resumed run repeats it")
 flags.DEFINE_string("train_data", "", "override getTrainData() (comma list: TFRecords, synthetic://, idx://, png://)")
