@@ -485,6 +485,56 @@ def test_convpool_exact(dev, K, grid_cap, N, H, W, Ci, ci, Co, co, pad, e, cap):
         _same(dx[..., :ci], ref[..., :ci], "dx")
 
 
+def _fold_inputs(dev, B, cin, e, seed, n=None):
+    """the LRN-backward folds at lrn_alpha = 0, lrn_bias = 1: dyadic images (n of them: a
+    resident set) and dL/d norm1, any finite pool1, codes uniform in 0..4"""
+    g = _gen(dev, seed)
+    x = xo.dyadic((n or B, 28, 28, cin), -8, 8, 4 + e, g, dev, density=0.5)
+    dn = xo.dyadic((B, 14, 14, 32), -4, 4, 3, g, dev, density=0.5)
+    p1 = torch.randn(B, 14, 14, 32, generator=g, device=dev) * 3.0
+    p1 = (p1 * torch.exp2(torch.randint(-8, 9, p1.shape, generator=g, device=dev).float())).to(BF)
+    codes = torch.randint(0, 5, (B, 14, 14, 32), generator=g, device=dev, dtype=torch.uint8)
+    return x, dn, p1, codes
+
+
+def _lrn_identity(K, p1, dn):
+    """the precondition of the fold tests, on the standalone kernel: with alpha = 0 and bias =
+    1 lrn_math.h's backward is sc = fma(0, s, 1) = 1, k = 0, d = fma(g, pw, -0), and the
+    bf16 rounding returns the bf16 g even if pw is an ulp off 1"""
+    P = dn.numel() // 32
+    assert bool(torch.isfinite(p1.float()).all())
+    for beta in (0.75, 0.5):
+        dx = _nan(P, 32, dev=dn.device, dtype=BF)
+        K.lrn_bwd(p1.view(P, 32), dn.view(P, 32), dx, P, 32, 4, 1.0, 0.0, beta, False)
+        _same(dx, dn.view(P, 32), ("lrn_bwd at alpha 0", beta))
+
+
+def _fold_reduce(K, slab, grid, cin, dev):
+    G, Ip, I, brow = K.convpool_reduce_args(cin, 32, 5, 2, 28, 28, cin)
+    dw = _nan(5, 5, cin, 32, dev=dev)
+    db = _nan(32, dev=dev)
+    K.splitk_reduce(slab, grid, K.convpool_rows(cin, 32, 5, 2, 28, 28), 32, G, Ip, I, 32, brow, dw, db, 1.0)
+    return dw, db
+
+
+@pytest.mark.parametrize("cin", [1, 3], ids=["cin1", "cin3"])
+@pytest.mark.parametrize("beta", [0.75, 0.5])
+@pytest.mark.parametrize("B,grid", [(5, 2), (77, 37)])
+def test_convpool_lrn_fold_exact(dev, K, B, grid, beta, cin):
+    """convpool_wgrad_k<..., LRNB> (beta 0.75: LRNB 2, else 1) with the LRN made the identity:
+    everything but the LRN math -- staging, un-pooling, the GEMM, the split-K slabs"""
+    x, dn, p1, codes = _fold_inputs(dev, B, cin, 0, 1050 + B + cin)
+    _lrn_identity(K, p1, dn)
+    rw, rb = xo.conv_wgrad(x, xo.unpool(dn, codes), 5, 5, "SAME", 7, 3)
+    KM = K.convpool_rows(cin, 32, 5, 2, 28, 28)
+    slab = _nan(grid * KM * 32, dev=dev)
+    K.convpool_wgrad(x, dn, codes, slab, grid, B, cin, 32, 5, 2, 28, 28, lrn_p=p1, lrn_bias=1.0, lrn_alpha=0.0,
+                     lrn_beta=beta, lrn_r=4)
+    dw, db = _fold_reduce(K, slab, grid, cin, dev)
+    _same(dw, xo.to_f32(rw), "dw")
+    _same(db, xo.to_f32(rb), "db")
+
+
 # ================================================================== lenet_band.hip
 def _lenet(dev, B, e=0):
     (x, w1, b1, w2, b2, dP2), fu, bu = xo.lenet_inputs(B, 1100 + B, dev, e)
@@ -537,6 +587,39 @@ def test_lenet_bwd_exact(dev, K, grid_cap, B, cap, e):
         assert got[4] == min(cap, (B + 7) // 8)
     for name, gk, wk in zip(("dW1", "db1", "dW2", "db2"), got[:4], want):
         _same(gk, xo.to_f32(wk), name)
+
+
+# ================================================================== refc1_wgrad.hip
+# (B, grid cap, extra shift, through idx): every path of the 2-image tile pipeline -- half a
+# tile; one tile; a partial last tile; one block over three tiles (both LDS buffers reused,
+# accumulators carried); two blocks over four tiles; 39 tiles uncapped; a resident set read
+# through repeated, out-of-order rows; the inputs scaled by 2**-4
+REFC1 = [(1, 0, 0, False), (2, 0, 0, False), (3, 0, 0, False), (5, 1, 0, False), (7, 2, 0, False), (77, 0, 0, False),
+         (7, 2, 0, True), (5, 1, 4, False)]
+
+
+@pytest.mark.parametrize("cin", [1, 3], ids=["cin1", "cin3"])
+@pytest.mark.parametrize("B,cap,e,idx", REFC1)
+def test_refc1_wgrad_exact(dev, K, grid_cap, B, cap, e, idx, cin):
+    """refc1_wgrad_k with the LRN made the identity (alpha 0, bias 1): the pool-window-phase
+    GEMM of unpool(dn, codes) against x, the bias row and the slab layout, bit for bit.  The
+    uint8 input mode is not dyadic after its normalisation and stays with
+    test_refc1_wgrad_gpu.test_refc1_wgrad_gathered_input."""
+    grid_cap(cap)
+    n = 11 if idx else None
+    xs, dn, p1, codes = _fold_inputs(dev, B, cin, e, 1900 + 10 * B + cin + e, n=n)
+    _lrn_identity(K, p1, dn)
+    rows = torch.tensor([9, 2, 2, 0, 10, 5, 2], device=dev) if idx else None
+    x = xs[rows] if idx else xs
+    rw, rb = xo.conv_wgrad(x, xo.unpool(dn, codes), 5, 5, "SAME", 7 + e, 3)
+    grid = K.refc1_wgrad_blocks(B)
+    assert grid == min(cap or grid, (B + 1) // 2)
+    slab = _nan(grid * (48 if cin == 1 else 80) * 32, dev=dev)
+    src = dict(idx=rows) if idx else {}
+    K.refc1_wgrad(xs.view(-1, 784 * cin) if idx else xs, dn, p1, codes, slab, grid, B, 1.0, 0.0, 0.75, cin=cin, **src)
+    dw, db = _fold_reduce(K, slab, grid, cin, dev)
+    _same(dw, xo.to_f32(rw), "dw")
+    _same(db, xo.to_f32(rb), "db")
 
 
 # ================================================================== refc1n_fwd_k / refc1n3_fwd_k

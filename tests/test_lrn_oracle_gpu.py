@@ -9,7 +9,8 @@ These kernels are the root of a chain of bitwise tests, which stay as they are:
     == lrn_pool_fwd_k / lrn_pool_bwd_k        test_kernels_gpu.test_lrn_pool_matches_two_step
        == lrn_pool14_fwd_k / lrn_pool14_bwd_k test_kernels_gpu.test_lrn_pool_packed
     == the refc1n* norm1 epilogue             test_refc1_fwd_gpu
-    == the refc1_wgrad and convpool LRN-backward folds   test_refc1_wgrad_gpu, test_executor_gpu
+  the refc1_wgrad and convpool LRN-backward folds are not in that chain (their dP1 never
+  leaves LDS): test_refc1_oracle_gpu holds them to this oracle through probe inputs
   lrn_f32_*_v4_k (here)
     == lrn_pool_f32_*_k, conv1_f32_wgrad_lrn_k           test_f32_gpu
 The fused LRN -> pool kernels are also held to the oracle directly here, pooled values,
