@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """norm2 -> pool2 of the reference CNN at the benchmark batch: the generic lrn_pool kernels vs
-the packed 14x14x64 ones (misc.hip lrn_pool14_*), CUDA-event timed, interleaved rounds, plus a
+the packed 14x14x64 ones (pool_lrn.hip lrn_pool14_*), CUDA-event timed, interleaved rounds, plus a
 device copy of the same bytes as the bandwidth yardstick.
 
     python bench/micro_lrnpool.py [--batch 16384]

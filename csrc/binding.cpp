@@ -1120,7 +1120,7 @@ void fused_optimizer(Tensor params, Tensor grads, Tensor mom, Tensor ema, Tensor
   }
   hip_ok(mnistx::fused_optimizer(P<float>(params), P<const float>(grads),
                                  (use_momentum || adaptive) ? P<float>(mom) : nullptr,
-                                 ema_max >= 0 ? P<float>(ema) : nullptr, BFm(bf), sv.data(), nseg, total,
+                                 ema_max >= 0 ? P<float>(ema) : nullptr, BFm(bf), sv.data(), nseg,
                                  P<const int64_t>(step), op, l2p, l2n, cur_stream(), has_fin ? &fa : nullptr,
                                  has_perm ? &pj : nullptr, two_slots ? P<float>(*slot2) : nullptr, clip, gnp,
                                  (float)lars_eta, tnp, scheduled ? &sched : nullptr),

@@ -1,5 +1,5 @@
 // Deterministic per-step cross-entropy statistics (loss sum, correct count, NaN
-// flag) shared by the softmax-CE kernel (misc.hip) and the fused dense head
+// flag) shared by the softmax-CE kernel (softmax_ce.hip) and the fused dense head
 // (mlp_head.hip).  Each block reduces its threads in a fixed tree, writes one
 // partial to `work`, and the last block to finish (ticket counter at
 // work[4 * CE_MAXB]) combines the partials in block order: bitwise identical

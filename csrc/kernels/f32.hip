@@ -6,7 +6,7 @@
 //   * one MFMA GEMM engine on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32
 //     accumulate) with operand "loaders" for dense fwd / dgrad / wgrad and the
 //     implicit-GEMM conv fwd / dgrad (flipped filter) / wgrad (im2col^T, split-K
-//     into deterministic fp32 slabs reduced by misc.hip splitk_reduce);
+//     into deterministic fp32 slabs reduced by splitk_reduce.hip splitk_reduce);
 //   * fp32 2x2/2 SAME max-pool fwd/bwd (argmax byte), LRN fwd/bwd across
 //     channels, softmax-CE with fp32 logit gradients (ce_stats.h partials) and the
 //     u8 -> fp32 batch gather/normalise.

@@ -1,6 +1,7 @@
 // The body of fused_opt_k, adaptive_opt_k<RULE>, clipped_opt_k<RULE> and layerwise_opt_k<RULE, SELF>
-// (misc.hip), included inside each kernel so that each compiles it as its own code, with the
-// kernel's parameters in scope:
+// (optimizer.hip), included inside each kernel so that each compiles it as its own code (a function
+// template in its place changes all 24 instances: contraction, the guard's load), with perm.h and
+// ticket.h included before it and the kernel's parameters in scope:
 //   params, grads, mom, slot2, ema, bf, tab, step_p, op, l2, fin, pj, gnorm, clip_norm, tnorm,
 //   lars_eta, lw_per, sc, and `constexpr int RULE`, `constexpr bool CLIP`, `constexpr bool LW_SELF`,
 //   `constexpr bool SCHED`.

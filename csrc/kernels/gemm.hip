@@ -24,7 +24,7 @@
 // Staging: register double-buffered (global -> VGPR for tile t+1 while the MFMAs
 // of tile t run from LDS), one barrier per K step; split-K over blockIdx.y for
 // the huge-K weight-gradient reductions (deterministic fp32 slabs, reduced by
-// splitk_reduce in misc.hip).  Tiles are mapped XCD-aware (common.h).
+// splitk_reduce in splitk_reduce.hip).  Tiles are mapped XCD-aware (common.h).
 //
 // Replaces the reference's TF Conv2D / Conv2DBackprop* / MatMul kernels
 // (call sites mnist_input.py:142,161,184,192,205).

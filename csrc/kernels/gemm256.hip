@@ -710,6 +710,15 @@ bool fill_ok(int M, int N, int min_tiles) {
 
 int gemm256_cus() { return num_cus(); }
 
+// The process-wide grid budget that every persistent kernel's launcher reads (launchers.h
+// cap_grid / reserve_cut); it lives with num_cus, the CU count it trims.
+static int g_grid_cap = 0;
+int grid_cap() { return g_grid_cap; }
+void set_grid_cap(int n) { g_grid_cap = n > 0 ? n : 0; }
+static int g_reserve_cus = 0;
+int reserve_cus() { return g_reserve_cus; }
+void set_reserve_cus(int n) { g_reserve_cus = n > 0 ? n : 0; }
+
 // Routing switch (A/B): MNISTX_GEMM256=0 starts with every dense GEMM on gemm.hip;
 // set_gemm256 flips it at run time (tests and benches compare both paths in one process).
 static int g_gemm256 = -1;

@@ -270,7 +270,7 @@ hipError_t f32_softmax_ce(const float* logits, int ldl, const int32_t* labels, i
 hipError_t f32_prep_images(const uint8_t* src, const int64_t* idx, const int32_t* lab_src, int B, int HW, int Csrc,
                            int Cdst, float* out, int32_t* lab_out, hipStream_t st);
 
-// ---- misc.hip
+// ---- input_prep.hip: the epoch shuffle and K10 input prep
 hipError_t perm_positions(int64_t* out, int64_t start, int n, int64_t N, uint32_t seed, int h, hipStream_t st,
                           const int32_t* lab_src = nullptr, int32_t* lab_out = nullptr);
 // 28x28x1 batch gather + normalise with the Feistel epoch shuffle fused in (rows are
@@ -279,6 +279,7 @@ hipError_t prep_images_perm(const uint8_t* src, const int32_t* lab_src, int B, i
                             uint32_t seed, int h, bf16_t* out, int32_t* lab_out, hipStream_t st);
 hipError_t prep_images(const uint8_t* src, const int64_t* idx, const int32_t* lab_src, int B, int HW, int Csrc,
                        int Cdst, bf16_t* out, int32_t* lab_out, hipStream_t st);
+// ---- pool_lrn.hip: max-pool (K6), LRN (K7) and the fused pair
 hipError_t maxpool_fwd(const bf16_t* x, int Nb, int H, int W, int C, int OH, int OW, bf16_t* y, uint8_t* arg,
                        hipStream_t st);
 hipError_t maxpool_bwd(const bf16_t* dy, const uint8_t* arg, const bf16_t* y, int relu_mask, int Nb, int H,
@@ -296,6 +297,7 @@ hipError_t lrn_pool_fwd(const bf16_t* x, int Nb, int H, int W, int C, int r, flo
 void lrn_set_packed(int on);
 hipError_t lrn_pool_bwd(const bf16_t* x, const bf16_t* dP, const uint8_t* arg, int Nb, int H, int W, int C, int r,
                         float bias, float alpha, float beta, int relu_mask, bf16_t* dx, hipStream_t st);
+// ---- softmax_ce.hip: softmax cross-entropy (K8)
 // work (optional): >= CE_WORK_FLOATS floats, zero-initialised once; makes the loss /
 // accuracy sums deterministic (per-block partials combined in block order, ce_stats.h)
 // defer_blocks (optional out): with it, the row kernel writes per-block partials only and
@@ -445,6 +447,7 @@ hipError_t mix_images(bf16_t* images, const int32_t* labels, int32_t* labels2, f
 // [n, 6] = (0 unmixed / 1 mixup / 2 CutMix, the bits of lam, x0, x1, y0, y1); for the tests
 hipError_t mix_params(int32_t* out, int n, int64_t pos0, int64_t seed, int64_t thr_p, const float* T, const int32_t* S,
                       hipStream_t st);
+// ---- splitk_reduce.hip
 // NOTE: many splits over a small output are pre-summed IN PLACE (the slab is scratch).
 hipError_t splitk_reduce(float* slab, int splits, int M, int N, int G, int Ipad, int I, int J,
                          int bias_row, float* wdst, float* bdst, float scale, hipStream_t st);
@@ -462,6 +465,7 @@ hipError_t splitk_reduce_multi(const RedSpec* specs, int n, hipStream_t st);
 void set_reduce_fused(int on);
 int reduce_fused_enabled();
 
+// ---- optimizer.hip: the fused optimizer (K9), its norm passes, the step finalize, the bf16 cast
 struct OptSeg {          // one trainable tensor inside the flat buffers
   int64_t off;           // offset in the flat fp32 buffers
   int64_t n;             // elements
@@ -511,7 +515,7 @@ enum { OPT_LARS = 4, OPT_LAMB = 5 };
 
 // The learning-rate schedule beyond the plain staircase, computed on the device from *step (a
 // captured launch replays its arguments, so a rate computed on the host would freeze).  With
-// t = *step, W = warmup, T = total, all in fp32 (sched_lr, misc.hip):
+// t = *step, W = warmup, T = total, all in fp32 (sched_lr, optimizer.hip):
 //   warm(t) = (t + 1) / W  if W > 0 and t < W, else 1
 //   x(t)    = 0 if t <= W;  1 if t >= T;  else (t - W) / (T - W)
 //   LR_STAIRCASE   base = lr0 * decay_rate ** (t / decay_steps)           (OptParams; T unused)
@@ -566,7 +570,7 @@ struct PermJob {
 // perm (optional): run that job in the same launch
 // slot2: the second slot buffer, needed by op.rule = OPT_ADAM / OPT_RMSPROP (which also need mom)
 hipError_t fused_optimizer(float* params, const float* grads, float* mom, float* ema, bf16_t* bf, const OptSeg* segs,
-                           int nseg, int64_t total, const int64_t* step, OptParams op, float* l2, int l2n, hipStream_t st,
+                           int nseg, const int64_t* step, OptParams op, float* l2, int l2n, hipStream_t st,
                            const FinArgs* fin = nullptr, const PermJob* perm = nullptr, float* slot2 = nullptr,
                            float clip_norm = 0.f, float* gnorm = nullptr, float lars_eta = 0.f, float* tnorm = nullptr,
                            const LrSched* sched = nullptr);   // sched: nullptr = the plain staircase; never with a guard

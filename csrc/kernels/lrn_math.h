@@ -1,5 +1,5 @@
 // LRN (tf.nn.local_response_normalization) building blocks shared by the LRN kernels
-// (misc.hip) and the kernels that fold an LRN into their staging (convpool.hip).
+// (pool_lrn.hip) and the kernels that fold an LRN into their staging (convpool.hip).
 // Channel-parallel: each lane owns 8 channels (one 16-byte bf16 vector) of a pixel,
 // the C/8 lanes of a pixel sit side by side inside one 16-lane DPP row, and the R
 // channels a window needs from the neighbouring vectors come over DPP row shifts

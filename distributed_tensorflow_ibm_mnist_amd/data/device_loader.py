@@ -159,7 +159,7 @@ def perm_positions(start: int, n: int, N: int, seed: int, device=None, out: Opti
     """Dataset rows of stream positions start..start+n-1: position p -> F_e(p mod N),
     e = p // N, F_e a 4-round keyed Feistel bijection on [0, 4^h) restricted to
     [0, N) by cycle walking.  Every epoch is a full permutation of the dataset.
-    On a GPU this is the ``perm_positions`` HIP kernel (misc.hip), bit-identical.
+    On a GPU this is the ``perm_positions`` HIP kernel (input_prep.hip), bit-identical.
     ``labels`` = (dataset labels, out labels): also gather the rows' labels (one
     launch on the GPU)."""
     h = _half_bits(N)
@@ -268,7 +268,7 @@ class DeviceLoader:
     def lookahead_job(self) -> Optional[tuple]:
         """The NEXT local batch's ``perm_positions`` job -- (rows out, dataset labels, labels out,
         start, N, seed, h) -- for the current step's optimizer launch to run in extra blocks
-        (``HipNet.next_input_job``, misc.hip ``PermJob``); the next ``next()`` then launches
+        (``HipNet.next_input_job``, launchers.h ``PermJob``); the next ``next()`` then launches
         nothing.  Only for the resident-dataset shuffle (``idx_out``) with full batches, and
         only where nothing else writes the index / label buffers between the optimizer and
         the next ``next()`` (bench.py; not the CLI loop, which evaluates into them)."""

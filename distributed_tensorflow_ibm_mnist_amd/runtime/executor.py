@@ -286,7 +286,7 @@ class LRNLayer(_Layer):
 
 
 class LRNPoolLayer(_Layer):
-    """LRN followed by a 2x2/2 SAME max-pool as ONE kernel each way (misc.hip
+    """LRN followed by a 2x2/2 SAME max-pool as ONE kernel each way (pool_lrn.hip
     lrn_pool_fwd_k / lrn_pool_bwd_k): the reference CNN's norm2 -> pool2
     (mnist_input.py:168-172).  The full-resolution LRN output and its gradient are
     never materialised; results are bitwise those of LRNLayer + PoolLayer."""
@@ -938,7 +938,7 @@ class HipNet:
 
     def update(self, grad_scale: float = 1.0, increment: bool = True, batch_for_stats: Optional[int] = None) -> None:
         # the step's finalize rides on the optimizer launch (its last block runs it: one launch
-        # fewer per step, misc.hip fused_opt_k; the launcher falls back to two launches)
+        # fewer per step, optimizer.hip fused_opt_k; the launcher falls back to two launches)
         # and, when a loader offers it (next_input_job: DeviceLoader.lookahead_job), the next
         # batch's shuffle rows + labels run in extra blocks of the same launch
         job = self.next_input_job() if getattr(self, "next_input_job", None) is not None else None

@@ -11,7 +11,7 @@ tiles (``conv_halo_f32.hip``, the bf16 halo design in fp32), conv1 (28x28x1 ->
 32) fwd / wgrad on shifted-copy image tiles (``conv1_f32.hip``); pool and LRN run
 as 16-byte-vector kernels.  At B=16384 that took the fp32 step from 26.0 to
 ~19 ms (``profiles/r3/fp32/``).  Optimizer, EMA, LR schedule, loss EMA and the
-deterministic split-K reduce are the shared K9 / misc.hip kernels, so the
+deterministic split-K reduce are the shared optimizer.hip (K9) / splitk_reduce.hip kernels, so the
 checkpoint layout, hooks and data-parallel buckets are identical.
 
 Layer semantics follow the reference graph exactly: conv + bias + ReLU

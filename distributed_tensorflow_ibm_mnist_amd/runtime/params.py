@@ -4,7 +4,7 @@ All trainable variables live in ONE contiguous fp32 buffer (and so do their
 gradients, momentum slots and EMA shadows), laid out in the reference's
 creation order (``mnist_input.py:137-205``).  This gives:
 
-* one fused optimizer launch for every tensor (K9, ``csrc/kernels/misc.hip``):
+* one fused optimizer launch for every tensor (K9, ``csrc/kernels/optimizer.hip``):
   L2 weight decay, SGD / momentum / Nesterov or Adam / RMSProp / Adagrad (TF1
   semantics; a second slot buffer where the rule has one), the staircase LR schedule
   (``mnist_input.py:252-256``, read from the device-side global step — no host
@@ -76,7 +76,7 @@ class OptConfig:
     # variable, biases included): scaled by clip_norm / max(global_norm, clip_norm).  None: off.
     clip_norm: Optional[float] = None
     lars_eta: float = 0.001       # lars: trust coefficient, r = eta * ||p|| / (||g|| + epsilon)
-    # the learning-rate schedule, a pure function of global_step t (lr_at; sched_lr in misc.hip):
+    # the learning-rate schedule, a pure function of global_step t (lr_at; sched_lr in optimizer.hip):
     #   lr(t) = warm(t) * base(t),  warm(t) = (t + 1) / warmup_steps for t < warmup_steps, else 1
     #   "staircase"   base = lr0 * decay_rate ** (t // decay_steps)
     #   "polynomial"  base = lr_end + (lr0 - lr_end) * (1 - x) ** lr_power
@@ -294,7 +294,7 @@ class FlatParams:
         self.bf16 = torch.zeros(max(bf_total, 1), dtype=torch.bfloat16, device=device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
         self.wd_entries = [e for e in entries if e.l2_index >= 0]
-        # [per-tensor sum(w^2) | one partial per fused-optimizer block (misc.hip OPT_CHUNK =
+        # [per-tensor sum(w^2) | one partial per fused-optimizer block (optimizer.hip OPT_CHUNK =
         # 512 elements)]: the partials are combined in block order (deterministic)
         n_opt_blocks = sum(-(-e.n // 512) for e in entries)
         self.l2 = torch.zeros(max(len(self.wd_entries), 1) + n_opt_blocks, dtype=torch.float32, device=device)

@@ -43,7 +43,7 @@ C_BF16_CAP = 2.0 ** -12 / U23
 
 REF_ALPHA = 0.001 / 9.0          # the model's constants (bias 1, beta 0.75)
 BIG_ALPHA = 0.05
-LRN_ALL = [(8, 4), (16, 4), (32, 4), (64, 4), (32, 2), (64, 2), (32, 5), (64, 5)]   # misc.hip LRN_ALL
+LRN_ALL = [(8, 4), (16, 4), (32, 4), (64, 4), (32, 2), (64, 2), (32, 5), (64, 5)]   # pool_lrn.hip LRN_ALL
 BETAS = [0.75, 0.5, 1.0]
 BIASES = [1.0, 2.0]
 ALPHAS = [REF_ALPHA, BIG_ALPHA]

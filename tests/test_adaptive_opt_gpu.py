@@ -1,4 +1,4 @@
-"""Adam / RMSProp / Adagrad in the fused optimizer launch (misc.hip adaptive_opt_k), on the GPU:
+"""Adam / RMSProp / Adagrad in the fused optimizer launch (optimizer.hip adaptive_opt_k), on the GPU:
 the kernel against a float64 oracle on a layout that hits every access path, the executors'
 wiring, hipGraph replay against eager (bitwise) and the training CLI with its checkpoint."""
 import importlib.util

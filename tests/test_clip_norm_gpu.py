@@ -1,4 +1,4 @@
-"""Gradient clipping by global norm in the fused optimizer step (misc.hip grad_sqnorm_k +
+"""Gradient clipping by global norm in the fused optimizer step (optimizer.hip grad_sqnorm_k +
 clipped_opt_k), on the GPU: the reduction against float64, the clipped update of every rule against
 the float64 oracle (tests/clip_oracle.py) on a layout that hits every access path, the exact
 identity at a huge threshold, the binding's validation, the executors' wiring, hipGraph replay

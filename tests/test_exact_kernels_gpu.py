@@ -13,7 +13,7 @@ Tie rules used here, from the kernel sources:
   v_max_f32 picks the winner -- "mantissa".  A raw sum of exactly +0 with a position embedded
   is a positive denormal; the extensions are built without any flush-to-zero flag (_build.py:
   -O3 only, fp32 denormals stay enabled), so zero sums order like positive ones.
-* misc.hip maxpool_fwd_k, f32.hip maxpool_f32_fwd_k, conv1_f32.hip conv1_f32_fwd_pool_k: a
+* pool_lrn.hip maxpool_fwd_k, f32.hip maxpool_f32_fwd_k, conv1_f32.hip conv1_f32_fwd_pool_k: a
   strict `>` scan in position order -- "first".
 """
 import pytest
@@ -650,7 +650,7 @@ def test_refc1n_pool1_exact(dev, K, grid_cap, cin, e):
 @pytest.mark.parametrize("N,H,W,C,e", [(4, 28, 28, 8, 0), (3, 14, 14, 64, 0), (2, 7, 7, 16, 0), (5, 10, 10, 16, 0),
                                        (2, 7, 7, 16, 4)])
 def test_maxpool_exact(dev, K, N, H, W, C, e):
-    """values, codes (ReLU zeros and repeated small integers tie all the time: misc.hip
+    """values, codes (ReLU zeros and repeated small integers tie all the time: pool_lrn.hip
     maxpool_fwd_k scans positions 0..3 with a strict `>`, so the first maximum wins) and the
     backward with and without the ReLU mask; 7 x 7 pools its last row / column alone"""
     g = _gen(dev, 1300 + H)

@@ -1,4 +1,4 @@
-"""Launch fusions of the step's tail (misc.hip):
+"""Launch fusions of the step's tail (splitk_reduce.hip, optimizer.hip):
 
 * the optimizer launch runs the step's finalize in its last block (agent-scope ticket),
   instead of a separate finalize_k launch -- the same code on the same partials, so the step

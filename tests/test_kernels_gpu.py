@@ -564,7 +564,7 @@ def test_lrn_pool_matches_two_step(dev, K, N, H, W, C, relu):
 
 @pytest.mark.parametrize("N", [1, 77, 40000])
 def test_lrn_pool_packed(dev, K, N):
-    """The packed 14x14x64 norm2 -> pool2 kernels (misc.hip lrn_pool14_fwd_k / _bwd_k: v_pk math,
+    """The packed 14x14x64 norm2 -> pool2 kernels (pool_lrn.hip lrn_pool14_fwd_k / _bwd_k: v_pk math,
     integer-key argmax on the post-ReLU input) == the generic lrn_pool kernels, bitwise: pooled
     values, argmax codes (ties included: bf16-rounded inputs repeat) and the input gradient.
     N = 40000 runs two grid-stride iterations at the 16384-block cap."""

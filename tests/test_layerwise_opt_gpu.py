@@ -1,4 +1,4 @@
-"""LARS and LAMB in the fused optimizer step (misc.hip var_sqnorm_k + var_ratio_k +
+"""LARS and LAMB in the fused optimizer step (optimizer.hip var_sqnorm_k + var_ratio_k +
 layerwise_opt_k), on the GPU: the per-variable reduction against float64, both rules against the
 float64 oracle (tests/layerwise_oracle.py) on a layout that hits every access path, the exact
 identity of lars at ratio 1 with momentum, the binding's validation, the executors' wiring,

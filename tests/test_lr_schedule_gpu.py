@@ -1,4 +1,4 @@
-"""Learning-rate warmup with polynomial and cosine decay on the device (misc.hip sched_lr, the
+"""Learning-rate warmup with polynomial and cosine decay on the device (optimizer.hip sched_lr, the
 *_sched_k optimizer kernels, lr_at_steps_k), on the GPU: the device's rate against the float64
 oracle (tests/lr_schedule_oracle.py), every kernel family applying exactly that rate and following
 the subclassed optimizer oracles across the warmup boundary, the defaults bit for bit, the

@@ -11,7 +11,7 @@ The two rules, read from the sources (not from what the kernels return):
   window position rides in the two low mantissa bits of the raw fp32 sum and a bare v_max_f32
   picks the winner.  Among equal positive sums the highest position has the largest bit
   pattern and wins; among equal negative sums the lowest.
-* "first" -- misc.hip maxpool_fwd_k / lrn_pool_fwd_k (`if (f > best[j])` over d = 0..3),
+* "first" -- pool_lrn.hip maxpool_fwd_k / lrn_pool_fwd_k (`if (f > best[j])` over d = 0..3),
   lrn_pool14_fwd_k (integer keys `bits << 16 | 3 - d`), f32.hip maxpool_f32_fwd_k and
   conv1_f32.hip conv1_f32_fwd_pool_k (`if (v[d] > bv)`): the first maximum wins.
 
@@ -146,7 +146,7 @@ def _tied_activations(dev, N, H, W, C, seed, dtype=BF):
 
 @pytest.mark.parametrize("N,H,W,C", [(4, 28, 28, 8), (3, 14, 14, 64), (2, 7, 7, 16)])
 def test_maxpool_ties(dev, K, N, H, W, C):
-    """maxpool_fwd_k (bf16) and maxpool_f32_fwd_k: the first maximum wins (misc.hip: `if (f >
+    """maxpool_fwd_k (bf16) and maxpool_f32_fwd_k: the first maximum wins (pool_lrn.hip: `if (f >
     best[j])`; f32.hip: `if (v > best)`), the two paths agree with each other"""
     x = _tied_activations(dev, N, H, W, C, 50 + H)
     ry, rarg = xo.maxpool2x2(x, "first")
