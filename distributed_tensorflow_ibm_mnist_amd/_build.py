@@ -1,7 +1,7 @@
 """In-tree build of the native extensions (no hipify, no JIT cache).
 
 * ``_kernels``  — HIP/CDNA4 kernels for gfx950 (``csrc/kernels/*.hip``, hipcc)
-                 + torch binding (``csrc/binding.cpp``).
+                 + torch binding (``csrc/bind/*.cpp``, one unit per subsystem, g++).
 * ``_host``     — host-side C++ runtime (``csrc/host/*.cpp``): crc32c, TFRecord
                  reader/writer, tf.Example codec, tensor-bundle (SSTable) I/O,
                  IDX parsing.  Pure C++ (g++), usable on CPU-only machines.
@@ -101,15 +101,19 @@ def build_kernels(force: bool = False, verbose: bool = True, jobs: int = 8) -> s
             jobs_list.append([HIPCC, "-std=c++17", "-O3", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-fPIC",
                               "-mllvm", "-amdgpu-mfma-vgpr-form",
                               "-D__HIP_PLATFORM_AMD__=1", f"-I{CSRC}", "-c", s, "-o", o])
-    bsrc = os.path.join(CSRC, "binding.cpp")
-    bobj = os.path.join(BUILD, "binding.o")
-    objs.append(bobj)
-    if force or _newer(bobj, [bsrc] + hdrs):
-        py_inc = sysconfig.get_paths()["include"]
-        jobs_list.append([CXX, "-std=c++17", "-O2", "-fPIC", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
-                          "-DTORCH_EXTENSION_NAME=_kernels", "-DTORCH_API_INCLUDE_EXTENSION_H",
-                          "-D_GLIBCXX_USE_CXX11_ABI=1", "-I/opt/rocm/include", f"-I{CSRC}", f"-I{py_inc}",
-                          *[f"-I{p}" for p in inc], "-c", bsrc, "-o", bobj])
+    # the torch binding, one unit per subsystem: only the objects listed here are linked
+    bdir = os.path.join(CSRC, "bind")
+    bhdrs = _headers(bdir) + hdrs
+    py_inc = sysconfig.get_paths()["include"]
+    for f in sorted(f for f in os.listdir(bdir) if f.endswith(".cpp")):
+        bsrc = os.path.join(bdir, f)
+        bobj = os.path.join(BUILD, f"bind_{f[:-4]}.o")
+        objs.append(bobj)
+        if force or _newer(bobj, [bsrc] + bhdrs):
+            jobs_list.append([CXX, "-std=c++17", "-O2", "-fPIC", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
+                              "-DTORCH_EXTENSION_NAME=_kernels", "-DTORCH_API_INCLUDE_EXTENSION_H",
+                              "-D_GLIBCXX_USE_CXX11_ABI=1", "-I/opt/rocm/include", f"-I{CSRC}", f"-I{py_inc}",
+                              *[f"-I{p}" for p in inc], "-c", bsrc, "-o", bobj])
     if verbose and jobs_list:
         print(f"[build] compiling {len(jobs_list)} unit(s) for {ARCH} ...", flush=True)
     with cf.ThreadPoolExecutor(max_workers=max(1, min(jobs, len(jobs_list) or 1))) as ex:
